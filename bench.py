@@ -10,12 +10,20 @@ grows).
 
 The timed image reads every stored matrix value from HBM on every step, as BCRSMatrix::mv does
 (kernels_cpp.hh:611-617): `--image arrays` (default) = the symmetric band arrays (EIG_MAT_NO_UNIFORM:
-the 4 upper diagonals, 32 B per row, lower entries through the mirrored slots).  At N = 1 the line
-also carries the same step on the SELL / CSR image (`csr`: values + column structure) and the
-constant-coefficient shortcut (`stencil_shortcut`: band values in the kernel arguments, no matrix
-bytes) -- side numbers, never `value` or `roofline`.
+the 4 upper diagonals, 32 B per row, lower entries through the mirrored slots).
 
-    python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, the
+result line (`value` = K / wall time of the timed steps, `ms_per_step` = that time / K in ms).
+`--dump-outputs DIR` then also writes what the timed path hands its caller after the last timed step
+(eig_lanczos_tridiag: DIR/alpha.npy and DIR/beta.npy, float64, of the W + K steps; matrix and start
+vector are generated from fixed seeds, so two builds can be compared array for array).
+`--full` adds every measurement that takes runs of its own: the standalone SpMV, the measured HBM
+copy rate, the per-launch kernel-event replay (N > 1), at N = 1 the same step on the SELL / CSR
+image (`csr`: values + column structure), the constant-coefficient shortcut (`stencil_shortcut`:
+band values in the kernel arguments, no matrix bytes) and a general matrix (`general`) -- side
+numbers, never `value` or `roofline` -- and the CPU baselines (`cpu_baseline`).
+
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -382,6 +390,14 @@ def main():
                     help="ranks (one per GPU); N > 1 without a launcher starts torch.distributed.run itself")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: standalone SpMV, measured HBM copy "
+                         "rate, per-launch kernel-event replay (N > 1), the side images and the CPU baselines "
+                         "(--side-steps, --general-steps, --cpu-*, --scipy-steps and --no-cpu-baseline size or "
+                         "skip these and mean nothing without --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path returns to its caller after its last "
+                         "step (eig_lanczos_tridiag of the W + K steps) as DIR/alpha.npy and DIR/beta.npy, float64")
     ap.add_argument("--N", type=int, default=256, help="grid points per axis (n = N^3)")
     ap.add_argument("--matrix", choices=["poisson", "varcoef"], default="poisson",
                     help="poisson: the 7-point Poisson matrix of the metric (eig_gen kind 4); varcoef: the "
@@ -430,6 +446,8 @@ def main():
                     help="timed steps as one hipGraph replay or launched one by one; auto = graph when "
                          "N > 1 (host-bound halo/allreduce calls), eager at N = 1 (measured faster there)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # decided before anything loads the HIP library or touches the GPU
         sys.exit(run_ranks(args.gpus, sys.argv[1:]))
@@ -650,12 +668,12 @@ def main():
     eager = args.launch == "eager" or (args.launch == "auto" and world == 1)
     # graph replay (the N > 1 default): the timed graph carries no per-launch events; a second,
     # short graph with per-launch event nodes is replayed after the timed region for the kernel
-    # timing, so the event packets do not sit between the timed kernels
-    K2 = min(K, 20) if kev and not eager else 0
+    # timing, so the event packets do not sit between the timed kernels (a run of its own: --full)
+    K2 = min(K, 20) if kev and not eager and args.full else 0
     ws = eigmi.LanczosWorkspace(M, W + K + K2, seed=123, fused=variant == "fused", pipelined=pipelined)
     if W:
         ws.step(W)
-    graph = False if eager else ws.capture(K, timed=kev and K2 == 0)
+    graph = False if eager else ws.capture(K, timed=False)
     k0, L0 = ws.info()
     barrier()
     ctx.sync()
@@ -678,6 +696,11 @@ def main():
         tim_k = tim
     alpha, beta = ws.tridiag()
     ok = bool(np.all(np.isfinite(alpha)) and np.all(beta[1:] > 0))
+    if args.dump_outputs and rank == 0:
+        # the coefficients as they stood after the last timed step (every rank holds the same ones)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "alpha.npy"), np.ascontiguousarray(alpha[:W + K], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "beta.npy"), np.ascontiguousarray(beta[:W + K + 1], dtype=np.float64))
 
     # dominant kernel: the step kernel (fused) or the SpMV kernel (classic), HIP events on the
     # library stream around every launch of the timed region
@@ -715,11 +738,11 @@ def main():
                     "csr_equiv_GBs": round(csr_bytes / (k1_ms * 1e-3) / 1e9, 1)}
     step_bytes = eigmi.bytes_lanczos_step(n, nnz_total)
     value = K / dt
-    # outside the timed region: the standalone SpMV (eig_mv = BCRSMatrix::mv) on the same image, and
-    # the measured HBM copy rate the roofline is also quoted against
+    # --full, outside the timed region: the standalone SpMV (eig_mv = BCRSMatrix::mv) on the same image,
+    # and the measured HBM copy rate the roofline is also quoted against
     spmv = None
     copy_GBs = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         x = M.window_vector(np.random.default_rng(0).standard_normal(cnt))
         y = M.window_vector()
         M.mv_timed(x, y, 3)
@@ -732,7 +755,7 @@ def main():
         x.free()
         y.free()
     sides = {}
-    if rank == 0 and world == 1 and args.side_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.side_steps > 0:
         # the same step on the other images of the same matrix (side numbers: never value / roofline)
         def side_traffic(ki):
             return committed_traffic(ki, N, world, build, args.image)
@@ -741,7 +764,7 @@ def main():
                 sides[key] = side_image(ctx, rp, c, v, img, args.side_steps, n, nnz_total, traffic=side_traffic)
         if args.general_steps > 0 and args.matrix == "poisson":
             sides["general"] = side_general(ctx, N, args.general_steps, side_traffic)
-    if rank == 0:
+    if args.full and rank == 0:
         copy_GBs = eigmi.stream_copy_GBs(ctx)
         if spmv:
             spmv["frac_vs_measured_copy"] = round(spmv["GBs"] / copy_GBs, 4)
@@ -755,6 +778,7 @@ def main():
         "n_gpus": world,
         "steps": K,
         "warmup": W,
+        "full": args.full,
         "ms_per_step": round(dt / K * 1e3, 4),
         "higher_is_better": True,
         "scaling": "strong",
@@ -795,7 +819,7 @@ def main():
         "comm": comm_summary(ctx, world, ab_check),
         "build": build,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cv, cdt, rel = cpu_baseline(N, rp, c, v, args.cpu_steps, alpha, fused)
         out["cpu_baseline"] = {"value": round(cv, 4), "unit": "iters/s", "cores": 1, "kind": "port",
                                "sample": f"{args.cpu_steps} Lanczos steps on the same {N}^3 matrix and start "

@@ -92,6 +92,16 @@ def test_ab_mismatch_disqualifies_a_wrong_transport():
     assert bench.ab_mismatch(bad, b, a, b) == float("inf")
 
 
+def test_options_full_dump_and_steps_are_checked_before_the_gpu():
+    """--full and --dump-outputs exist, and a run that could time no step is refused by the argument
+    parser (exit 2) before the HIP library is loaded."""
+    bench = os.path.join(ROOT, "bench.py")
+    h = subprocess.run([sys.executable, bench, "--help"], capture_output=True, timeout=120)
+    assert h.returncode == 0 and b"--full" in h.stdout and b"--dump-outputs DIR" in h.stdout
+    p = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "0"], capture_output=True, timeout=120)
+    assert p.returncode == 2 and b"--steps" in p.stderr and p.stdout.strip() == b""
+
+
 def test_gpus_2_launches_a_child_and_fails_on_mismatch(tmp_path):
     """End to end on the CPU: `bench.py --gpus 2` without WORLD_SIZE must start the launcher (here a
     stand-in torch.distributed module on PYTHONPATH that prints a one-rank line) and exit 4 because

@@ -8,7 +8,7 @@
 # tasks:
 #   tests[:<file,file>]  pytest -m gpu (all, or the listed tests/ files)       -> tests.log
 #   smoke                __graft_entry__.smoke()                              -> smoke.log
-#   bench                python bench.py (the driver's default line)          -> bench.json
+#   bench                python bench.py --full (headline + every side measurement) -> bench.json
 #   profile              rocprofv3 kernel trace + FETCH / WRITE PMC passes of the bench (tools/profile_round.sh)
 #   configs              tools/bench_configs.py c1 c2 c3, c5 (256^3), inv (64^2, 200^2)  -> cfg_*.jsonl
 #   boxsegs              box kernels' z segments per tile column swept (tools/box_segs.py) -> box_segs.jsonl
@@ -74,7 +74,7 @@ run_task() {
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 ;;
     bench)
-      timeout -k 10 400 python bench.py > "$O/bench.json" 2> "$O/bench.err" ;;
+      timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" ;;
     profile)
       bash tools/profile_round.sh "$TAG" > "$O/profile.log" 2>&1 ;;
     configs)
