@@ -274,8 +274,9 @@ struct eig_mat_s {
   // stencil of config C5) derive the masks from the coordinates
   unsigned sym_box27 = 0;
   // packed copy of the 4 value arrays of a 7-point band ({+D, 0, +1, +nx} per row, 32 B; the P1 Kuhn
-  // band: 8 arrays, 64 B) for the value marches 15 / 16 / 18 / 19 (k_spmv.hip sym_pack_prepare: built
-  // at the first launch that marches on it, never by a query; refilled in place by a shift)
+  // band: 8 arrays, 64 B) for the march variants whose values are kMarchPack (march_variants.h;
+  // k_spmv.hip sym_pack_prepare: built at the first launch that marches on it, never by a query;
+  // refilled in place by a shift)
   double *sym_pack = nullptr;
   eigmi::i64 sym_pack_bytes = 0;
   // SELL image: padded entries of the explicit-column slices (their 4-B column indices are streamed)
@@ -286,7 +287,7 @@ struct eig_mat_s {
   eigmi::i64 mz0 = 0, mz1 = 0;
   int tune_march_runs = 0;  // eig_mat_tune(EIG_TUNE_MARCH_RUNS): plane runs per column, 0 = automatic
   int tune_halo_whole = 0;      // eig_mat_tune(EIG_TUNE_HALO): 1 = exchange first, then one whole launch
-  int tune_march_prefetch = 0;  // eig_mat_tune(EIG_TUNE_MARCH_PREFETCH): geometric march variant, 0 = automatic
+  int tune_march_prefetch = 0;  // eig_mat_tune(EIG_TUNE_MARCH_PREFETCH): asks march_select (k_spmv.hip) for a variant of march_variants.h, 0 = automatic
   int tune_cache = 0;           // eig_mat_tune(EIG_TUNE_CACHE): cache-policy bits of the march streams (measurement)
   int tune_box_cols = 0;    // eig_mat_tune(EIG_TUNE_BOX_COLS): columns per box-image workgroup (16 / 32), 0 = automatic
   int tune_box_map = 0;     // eig_mat_tune(EIG_TUNE_BOX_MAP): 1 = XCD-contiguous tile map of k_box_mv32 (measurement)
@@ -432,10 +433,14 @@ void lanczos_kernel_info(const eig_mat_s &A, bool fused, std::string &name, i64 
 i64 sell_image_bytes(const eig_mat_s &A);
 // Build what a march launch on A streams beside the band arrays (the value pack), ahead of a capture
 void march_prepare(const eig_mat_s &A);
-// whether the P1 Kuhn value pack (64 B per row) fits the 32-bit buffer descriptor march 16 / 19 read it by
+// The plane-march variant (march_variants.h) a launch on A takes (fused: the fused step; else eig_mv /
+// K1).  A pure function of A's fields: `distributed` stands for A.ctx->distributed(), so host tests
+// call it without a context or a device.
+int march_select(const eig_mat_s &A, bool fused, bool distributed);
+// whether the P1 Kuhn value pack (64 B per row) fits the 32-bit buffer descriptor its marches read it by
 bool kuhn_pack_fits(const eig_mat_s &A);
-// The P1 Kuhn march variant of a matrix the Kuhn march applies to (k_spmv.hip march_uniform): 16 / 19
-// on the value pack, 12 on the band arrays
+// march_select's choice among the P1 Kuhn variants for a matrix the Kuhn march applies to: the value
+// pack where it fits, else the band arrays
 int kuhn_variant(const eig_mat_s &A);
 // Whether EIG_LANCZOS_AUTO takes the fused step on this image: every 1x1 image (round 3: without
 // register spills the fused step beats the two-kernel step on scattered images too).

@@ -13,6 +13,7 @@
 // Work split: a workgroup of 4 waves walks a CONTIGUOUS chunk of slices (waves interleaved), so
 // rows that share x lines stay in one CU / one XCD's L2; 2048 workgroups (8 per CU) are resident.
 #include "internal.h"
+#include "march_variants.h"
 #include "reduce_dev.h"
 #include "xch_dev.h"
 
@@ -1122,11 +1123,11 @@ struct MarchPlan {
   // in-grid neighbours are exactly the stored entries -- the march derives each row's mask from
   // its coordinates instead of loading it; gz0 = the global plane of the rank's first row
   int gx, gy, gz, gz0;
-  int uni;  // the march variant the launch takes (march_uniform: 0 arrays, 1 loaded masks, 2..9 geometric)
+  int uni;  // the march variant the launch takes (march_select; march_variants.h says what each is)
   // results stored with plain (MALL-allocating) stores instead of nontemporal ones: the vectors of a
   // small grid stay in the 256 MB memory-side cache for the next launch (geo2 kernels)
   int tstore;
-  // box marches (variant 12): band array of the upper offset at 27-box position (a+1) 9 + (b+1) 3 + (c+1),
+  // box marches (the Kuhn variants): band array of the upper offset at 27-box position (a+1) 9 + (b+1) 3 + (c+1),
   // -1 when the stencil does not store it
   signed char kj[27];
   const double *pack;
@@ -1148,7 +1149,7 @@ __device__ __forceinline__ void march_store(const MarchPlan &mp, T v, T *p)
     __builtin_nontemporal_store(v, p);
 }
 
-// Geometric uniform-band march with the +D operand loaded PF + 1 planes ahead (UNI = 2 + PF;
+// Geometric uniform-band march with the +D operand loaded PF + 1 planes ahead (march variants 3 .. 6;
 // eig_mat_tune(EIG_TUNE_MARCH_PREFETCH)).  The plain march waits for every load of plane z --
 // including the +D pair that only arrives from HBM -- and, at the loop head, for the store of
 // plane z - 1 (one vmcnt counter, in order), so a wave has one plane's memory in flight.  Here the
@@ -1498,7 +1499,6 @@ __device__ __forceinline__ void march_rows_geo2(const SellB1 &A, const MarchPlan
 // per column on wide planes (march_plan, round 6) 4 M rows 45.6 vs 46.0 us, 2 M rows 27.6 either way --
 // the threshold is 4 M.
 constexpr bool kMarch2lDefault = true;
-constexpr bool is_march2l(int uni) { return uni == 22 || uni == 23 || uni == 24; }
 
 template <class X, class EPI, class PRE>
 __device__ __forceinline__ void march_rows_geo2_2l(const SellB1 &A, const MarchPlan &mp, i64 own, int lane, int wave,
@@ -1611,9 +1611,6 @@ __device__ __forceinline__ void march_rows_geo2_2l(const SellB1 &A, const MarchP
 // y - 1 (planes z and z - 1).  Missing neighbours read as exact zeros (zero-record descriptors for
 // lines / planes outside the grid, out-of-range edge offsets at x = 0 / nx - 1), so each row sums its
 // stored entries in ascending-column order bit for bit as the reference row loop.
-constexpr unsigned kKuhn15 = (1u << 0) | (1u << 1) | (1u << 3) | (1u << 4) | (1u << 9) | (1u << 10) | (1u << 12) |
-                             (1u << 13) | (1u << 14) | (1u << 16) | (1u << 17) | (1u << 22) | (1u << 23) |
-                             (1u << 25) | (1u << 26);
 // KP (march variant 16): the values from the Kuhn pack (mp.pack: four arrays of value pairs (0, +1),
 // (+nx, +nx+1), (+D, +D+1), (+D+nx, +D+nx+1) per window row -- 4 instead of 8 16-B/8-B streams and
 // 2 instead of 4 gathers) through 64-bit global addresses, lane 0's edge values by exec-masked loads.
@@ -1847,6 +1844,15 @@ __device__ __forceinline__ void march_rows_kuhn(const SellB1 &A, const MarchPlan
   }
 }
 
+// A variant's traits as namespace-scope constants for the kernels below (a local constexpr copy
+// would be one more stack object in each kernel before optimisation)
+template <int UNI>
+constexpr MarchTraits kTraits = march_traits(UNI);
+template <int UNI>
+constexpr bool kWholePlanes = kTraits<UNI>.whole_planes();
+template <int UNI>
+constexpr bool kUniformValues = kTraits<UNI>.values == kMarchUniform;
+
 // The rows of this wave's work item, in plane order: epi(r, w, acc, centre) gets each row's sum
 // and its own operand x[w] (raw: a double, or the (t, u) pair of the fused step).
 // The first entry of both far spans is issued with the row's streams, so a 7-point row waits
@@ -1864,31 +1870,31 @@ template <class MT, int KC, bool SPAN1, int UNI, class X, class EPI, class PRE =
 __device__ __forceinline__ void march_rows(const SellB1 &A, const MarchPlan &mp, i64 own, int lane, int wave,
                                            const X &x, EPI &epi, PRE &&pre = PRE{})
 {
-  static_assert(!UNI || SPAN1 || UNI == 12 || UNI == 16 || UNI == 19 || UNI == 20 || is_march2l(UNI),
-                "uniform-band march: far spans of at most one offset");
-  if constexpr (UNI == 12 || UNI == 16 || UNI == 19 || UNI == 20)
+  static_assert(kTraits<UNI>.valid, "not a march variant (march_variants.h)");
+  static_assert(kTraits<UNI>.any_head() ||
+                    (SPAN1 == kTraits<UNI>.span1() && (int)sizeof(MT) == kTraits<UNI>.mask_bytes()),
+                "march variant instantiated with another template head than its traits name");
+  if constexpr (kTraits<UNI>.family == kMarchKuhn)
   {
-    march_rows_kuhn<UNI != 12, UNI == 20>(A, mp, own, lane, wave, x, epi, pre);
+    march_rows_kuhn<kTraits<UNI>.kp, kTraits<UNI>.lx>(A, mp, own, lane, wave, x, epi, pre);
     return;
   }
-  else if constexpr (is_march2l(UNI))
+  else if constexpr (kTraits<UNI>.family == kMarchGeo2L2)
   {
     march_rows_geo2_2l(A, mp, own, lane, wave, x, epi, pre);
     return;
   }
-
-  else if constexpr (UNI >= 3)
+  else if constexpr (kTraits<UNI>.family == kMarchGeo2)
   {
-    // 3, 4, 5: +D operand 1, 2, 3 planes ahead; 6: 3 planes ahead and the gathers one plane ahead
-    if constexpr (UNI >= 10)  // 10, 11: the value march (band arrays streamed), 11 one plane ahead, 13 packed
-      march_rows_geo2<0, false, UNI == 14 ? 4 : UNI == 15 || UNI == 18 ? 5 : UNI - 9>(A, mp, own, lane, wave, x, epi, pre);
-    else if constexpr (UNI >= 7)  // 7, 8, 9: march_rows_geo2 with the prefetches of 3, 4, 6
-      march_rows_geo2<UNI == 9 ? 2 : UNI - 7, UNI == 9, 0>(A, mp, own, lane, wave, x, epi, pre);
-    else
-      march_rows_geo<UNI == 6 ? 2 : UNI - 3, UNI == 6>(A, mp, own, lane, wave, x, epi);
+    march_rows_geo2<kTraits<UNI>.pf, kTraits<UNI>.pg, kTraits<UNI>.val>(A, mp, own, lane, wave, x, epi, pre);
     return;
   }
-  constexpr bool GEO = UNI == 2;
+  else if constexpr (kTraits<UNI>.family == kMarchGeo)
+  {
+    march_rows_geo<kTraits<UNI>.pf, kTraits<UNI>.pg>(A, mp, own, lane, wave, x, epi);
+    return;
+  }
+  constexpr bool GEO = kTraits<UNI>.geo_masks;
   typedef typename X::raw raw;
   // 32-bit row / window indices (window < 2^31, enforced at upload) keep the address math short
   const SymImg &S = A.sym;
@@ -1940,7 +1946,7 @@ __device__ __forceinline__ void march_rows(const SellB1 &A, const MarchPlan &mp,
     else
       st.m = r < mrows ? (unsigned)__builtin_nontemporal_load(mask + (unsigned)r) : 0u;
     st.pD = x.load(cx(w + D));
-    if constexpr (UNI)
+    if constexpr (kUniformValues<UNI>)
     {
       st.aD = mp.cD;
       st.a0 = mp.c0;
@@ -1956,7 +1962,7 @@ __device__ __forceinline__ void march_rows(const SellB1 &A, const MarchPlan &mp,
   // carried operands: the -D operand (as its value x.val), its mirrored matrix entry, the centre
   int w = own32 + col * 64 + lane + z0 * D;
   double pmv = x.val(x.load(cx(w - D)));
-  double amD = UNI ? mp.cD : UD[cv(w - D)];
+  double amD = kUniformValues<UNI> ? mp.cD : UD[cv(w - D)];
   raw pcur = x.load(cx(w));
   Stream cur;
   const bool edge = lane == 0 || lane == 63;
@@ -1969,18 +1975,18 @@ __device__ __forceinline__ void march_rows(const SellB1 &A, const MarchPlan &mp,
     raw eg;
     double ae = 0.0;
     if (edge) eg = x.load(cx(lane == 0 ? w - 1 : w + 1));
-    if (lane == 0) ae = UNI ? mp.c1 : U1[cv(w - 1)];
+    if (lane == 0) ae = kUniformValues<UNI> ? mp.c1 : U1[cv(w - 1)];
     double an = 0.0, aq = 0.0;
     raw xn, xq;
     if (mp.dn)
     {
       const unsigned g = cx(w + mp.dn);  // (negative offset: the mirrored slot at the gathered row)
-      an = UNI ? mp.cn : mp.Un[g];
+      an = kUniformValues<UNI> ? mp.cn : mp.Un[g];
       xn = x.load(g);
     }
     if (mp.dq)
     {
-      aq = UNI ? mp.cq : mp.Uq[wv];
+      aq = kUniformValues<UNI> ? mp.cq : mp.Uq[wv];
       xq = x.load(cx(w + mp.dq));
     }
     const unsigned m = cur.m;
@@ -2019,7 +2025,7 @@ __device__ __forceinline__ void march_rows(const SellB1 &A, const MarchPlan &mp,
 
 // y[own + r] = (A x)[r] on the plane march (BCRSMatrix::mv; bitwise k_spmv_b1).
 // resident waves per SIMD of the eig_mv / K1 march kernels (the box march holds ~90 VGPRs)
-constexpr int march_mv_waves(int uni) { return uni == 12 || uni == 16 || uni == 19 || uni == 20 || is_march2l(uni) ? 5 : 8; }
+constexpr int march_mv_waves(int uni) { return march_traits(uni).mv_waves; }
 
 template <class MT, bool SPAN1, int UNI>
 __global__ __launch_bounds__(kStreamThreads, march_mv_waves(UNI)) void k_spmv_march(i64 nrows, i64 own, SellB1 A, MarchPlan mp,
@@ -2028,9 +2034,9 @@ __global__ __launch_bounds__(kStreamThreads, march_mv_waves(UNI)) void k_spmv_ma
 {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   auto epi = [&](int r, int w, double acc, double) {
-    if constexpr (UNI >= 7)
+    if constexpr (kTraits<UNI>.geo2_path())
       march_store(mp, acc, y + (unsigned)w);  // (geometric: whole planes)
-    else if (UNI >= 3 || r < nrows)
+    else if (kWholePlanes<UNI> || r < nrows)
       __builtin_nontemporal_store(acc, y + (unsigned)w);
   };
   march_rows<MT, 2, SPAN1, UNI>(A, mp, own, lane, wave, XPlain{x}, epi);
@@ -2075,11 +2081,7 @@ __global__ __launch_bounds__(kStreamThreads, march_mv_waves(UNI)) void k_lanczos
 // launch (fused_begin) takes the rows of the planes this launch marches.  Built for 7 waves / SIMD
 // (72 VGPRs; at 8 the pair operands spill: -5 %).
 // resident waves per SIMD the fused march kernels are built for (registers: no spills)
-constexpr int march_fused_waves(int uni)
-{
-  return uni == 22 ? 5 : uni == 23 ? 4 : uni == 24 ? 6 : uni == 18 ? 7 : uni == 16 || uni == 20 ? 4 : uni == 12 || uni == 19 ? 5 : uni == 11 ? 5 : uni == 10 || uni >= 13 ? 6 : uni == 6 || uni == 9 ? 4 : uni == 5 ? 5 : uni == 4 || uni == 8 ? 6
-       : uni == 3 || uni == 7 ? 7 : uni ? 8 : 7;
-}
+constexpr int march_fused_waves(int uni) { return march_traits(uni).fused_waves; }
 
 template <class MT, bool SPAN1, int UNI>
 __global__ __launch_bounds__(kStreamThreads, march_fused_waves(UNI)) void k_lanczos_fused_march(
@@ -2089,7 +2091,7 @@ __global__ __launch_bounds__(kStreamThreads, march_fused_waves(UNI)) void k_lanc
   __shared__ double tot[3];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double d = 0.0, q2 = 0.0, m2 = 0.0;
-  if constexpr (UNI >= 7)
+  if constexpr (kTraits<UNI>.geo2_path())
   {
     // geo2: the scalar prologue runs while the wave's first plane loads are in flight (the march
     // calls `pre` after issuing them); waves without a work item run it after the march returns
@@ -2148,7 +2150,7 @@ __global__ __launch_bounds__(kStreamThreads, march_fused_waves(UNI)) void k_lanc
   else
   {
     auto epi = [&](int r, int w, double acc, dpair pc) {
-      if (UNI >= 3 || r < nrows)  // (geometric images cover whole planes: no row test)
+      if (kWholePlanes<UNI> || r < nrows)  // (geometric images cover whole planes: no row test)
       {
         const double uk = pc.x - c * pc.y;
         double ti = (acc - mu * uk) * sig;
@@ -2592,7 +2594,8 @@ static int grid_for_slices(K kernel, i64 count, int num_cu)
   return (int)(need < cap ? need : cap);
 }
 
-// The packed value image of march variants 13 / 15: two arrays of value pairs, (+D, 0) and (+1, +nx)
+// The packed value image of the 7-point pack marches (MarchTraits::needs_pack): two arrays of value
+// pairs, (+D, 0) and (+1, +nx)
 // per window row (the 5-point 2-D band: +nx = 0), so a wave reads each with one 16-B load per lane
 // of 1 KB contiguous; built from the band arrays at first use, freed by a shift.
 __global__ void k_sym_pack(i64 ld, const double *__restrict__ UD, const double *__restrict__ U0,
@@ -2604,7 +2607,7 @@ __global__ void k_sym_pack(i64 ld, const double *__restrict__ UD, const double *
     reinterpret_cast<dpair *>(out)[ld + w] = dpair{U1[w], Uq ? Uq[w] : 0.0};
   }
 }
-// Kuhn pack (march variant 16): four pair arrays, (0, +1), (+nx, +nx+1), (+D, +D+1), (+D+nx, +D+nx+1)
+// Kuhn pack (the Kuhn variants with KP): four pair arrays, (0, +1), (+nx, +nx+1), (+D, +D+1), (+D+nx, +D+nx+1)
 __global__ void k_kuhn_pack(i64 ld, const double *__restrict__ val, int4 ja, int4 jb, double *__restrict__ out)
 {
   const int j0[4] = {ja.x, ja.z, jb.x, jb.z}, j1[4] = {ja.y, ja.w, jb.y, jb.w};
@@ -2613,20 +2616,24 @@ __global__ void k_kuhn_pack(i64 ld, const double *__restrict__ val, int4 ja, int
     for (int q = 0; q < 4; ++q)
       reinterpret_cast<dpair *>(out)[(i64)q * ld + w] = dpair{val[(i64)j0[q] * ld + w], val[(i64)j1[q] * ld + w]};
 }
-static bool march_kuhn(const eig_mat_s &A);
+// Band array of the offset a D + b nx + c at 27-box position q = (a + 1) 9 + (b + 1) 3 + (c + 1), -1
+// when the band does not store it
+static int box_band_array(const eig_mat_s &A, i64 D, int q)
+{
+  const i64 off = (i64)(q / 9 - 1) * D + (i64)((q / 3) % 3 - 1) * A.sym_gx + (q % 3 - 1);
+  for (int k = 0; k < A.sym_nd; ++k)
+    if (A.sym_off[k] == off) return A.sym_dj[k];
+  return -1;
+}
 void sym_pack_fill(eig_mat_s &A, hipStream_t s)
 {
   if (A.sym_box27 == kKuhn15)
   {
     // band array of each upper Kuhn offset (the 27-box positions 13 14 | 16 17 | 22 23 | 25 26)
     const i64 D = (i64)A.sym_gx * A.sym_gy;
-    int j[27];
-    for (int q = 0; q < 27; ++q) j[q] = 0;
-    for (int k = 0; k < A.sym_nd; ++k)
-      for (int q = 13; q < 27; ++q)
-        if ((i64)(q / 9 - 1) * D + (i64)((q / 3) % 3 - 1) * A.sym_gx + (q % 3 - 1) == A.sym_off[k]) j[q] = A.sym_dj[k];
+    auto j = [&](int q) { return std::max(0, box_band_array(A, D, q)); };
     hipLaunchKernelGGL(k_kuhn_pack, dim3(2048), dim3(256), 0, s, A.sym_ld, A.sym_val,
-                       make_int4(j[13], j[14], j[16], j[17]), make_int4(j[22], j[23], j[25], j[26]), A.sym_pack);
+                       make_int4(j(13), j(14), j(16), j(17)), make_int4(j(22), j(23), j(25), j(26)), A.sym_pack);
     EIG_HIP(hipGetLastError());
     return;
   }
@@ -2656,7 +2663,8 @@ const double *sym_pack_prepare(const eig_mat_s &Ac)
 
 // EIG_MAT_NO_MARCH: the plane-marching kernels are off for this matrix (the slice kernels run).
 static bool march_enabled(const eig_mat_s &A) { return (A.kflags & EIG_MAT_NO_MARCH) == 0; }
-static bool march_span1(const eig_mat_s &A)
+// Far spans of the ascending offset list: the offsets [1, klo) lie in (-D, -1), [khi, nd - 1) in (+1, +D)
+static std::pair<int, int> far_spans(const eig_mat_s &A)
 {
   int klo = A.sym_nd, khi = A.sym_nd;
   for (int k = A.sym_nd - 1; k >= 0; --k)
@@ -2664,42 +2672,25 @@ static bool march_span1(const eig_mat_s &A)
     if (A.sym_off[k] >= -1) klo = k;
     if (A.sym_off[k] > 1) khi = k;
   }
-  return A.sym_mask_bytes == 1 && klo - 1 <= 1 && (A.sym_nd - 1) - khi <= 1;
+  return {klo, khi};
 }
-
 // Far spans of at most one offset each (u8-mask bands only: at most 8 offsets, so (-D, -1) and
 // (+1, +D) hold at most one offset each exactly when nd <= 7 with -1/0/+1 present).
-// Uniform band values in the march kernels' arguments (EIG_MAT_NO_UNIFORM keeps the array loads).
-// 0 = the arrays, 1 = uniform values + loaded row masks, 2 = uniform values + geometric row masks
-// (the grid coordinates of the global rows: a rank's slab starts at global plane sym_gz0);
-// 3 / 4 / 5: geometric, march_rows_geo with the +D operand 1 / 2 / 3 planes ahead, 6: 3 planes
-// ahead and the gathers 1 plane ahead (eig_mat_tune(EIG_TUNE_MARCH_PREFETCH) = 1 forces 2, 2..5
-// force 3..6; 0 = kGeoAuto).
-// 7 / 8 / 9: march_rows_geo2 (no masks or selects; x extent a multiple of 64, window < 2 GiB) with
-// the prefetches of 3 / 4 / 6 (tune values 6..8); a geo2 request on a grid that does not qualify
-// takes the corresponding march_rows_geo variant.
-// Automatic choice (measured: profiles/r03bj_march_variants.jsonl, r03bn_*, r03bp_*; tools/gpu.sh
-// prefetch): geo2 without prefetch (7) where the grid allows it -- fused step 256^3 125.8 us at 8
-// plane runs (plain march 130.0), 128^3 20.1 us (plain 30.2; with the MALL-resident plain stores,
-// MarchPlan::tstore), one rank's 256^2 x 32 slab 20.5 us (plain 34.5); eig_mv 256^3 46.1 us (plain
-// 59.4), 128^3 8.0 (12.1).  The prefetching geo2 variants (8, 9) are within a few per cent either
-// way.  Grids geo2 does not take: march_rows_geo with the +D operand two planes ahead (4).
-// 10 / 11: bands that are not uniform (or EIG_MAT_NO_UNIFORM) on a geo2 grid: the value march
-// (march_rows_geo2<VAL>: the band arrays streamed, masks from the coordinates), 11 with the value
-// streams and the +D operand one plane ahead (tune values 9 / 10; 1 = the plain masked march).
-// 12: the P1 Kuhn box march (march_rows_kuhn; eig_mat_s::sym_box27 == kKuhn15, one rank).
-static bool march_kuhn(const eig_mat_s &A)
+static bool march_span1(const eig_mat_s &A)
 {
-  return A.sym_box27 == kKuhn15 && A.sym_nd == 15 && !A.ctx->distributed() && A.sym_gx % 64 == 0 &&
-         A.window * 16 < (i64(1) << 31) && A.sym_ld * 8 < (i64(1) << 31) && A.tune_march_prefetch != 1;
+  const auto [klo, khi] = far_spans(A);
+  return A.sym_mask_bytes == 1 && klo - 1 <= 1 && (A.sym_nd - 1) - khi <= 1;
 }
-bool kuhn_pack_fits(const eig_mat_s &A) { return A.sym_ld * 64 < (i64(1) << 31); }
-// the Kuhn march on its value pack (16): fused step 256^3 346 us, eig_mv 292 us (the arrays, 12: 407 /
-// 330 us; profiles/r04d_p1k.jsonl); tune value 14 = the arrays, 15 = the pack variant 19.
-// The pack is read through one 32-bit buffer descriptor of 64 B per row: grids of 2^25 rows and
+// every vector a launch touches fits in half of the 256 MB MALL (MarchPlan::tstore)
+static bool vectors_fit_mall(const eig_mat_s &A) { return A.window * 16 * 3 <= (i64(128) << 20); }
+
+// The Kuhn pack is read through one 32-bit buffer descriptor of 64 B per row: grids of 2^25 rows and
 // more (e.g. 448^3, or 256 x 512 x 512, whose descriptor size would wrap to 0) take the arrays.
-// Default 20 (the pack with the line exchange in LDS) where the lines come in groups of 4: 256^3 fused
-// step 333.2 vs 340.8 us, eig_mv 278.7 vs 292.2 us (profiles/r05g_p1k.jsonl); tune value 13 = 16.
+bool kuhn_pack_fits(const eig_mat_s &A) { return A.sym_ld * 64 < (i64(1) << 31); }
+// The variant of an image the Kuhn march applies to.  On its value pack (16): fused step 256^3 346 us,
+// eig_mv 292 us (the arrays, 12: 407 / 330 us; profiles/r04d_p1k.jsonl).  Default 20 (the line exchange
+// in LDS) where the lines come in groups of 4: 256^3 fused step 333.2 vs 340.8 us, eig_mv 278.7 vs
+// 292.2 us (profiles/r05g_p1k.jsonl).  Tune values: 13 = 16, 14 = the arrays, 15 = 19.
 int kuhn_variant(const eig_mat_s &A)
 {
   const int tp = A.tune_march_prefetch;
@@ -2707,84 +2698,91 @@ int kuhn_variant(const eig_mat_s &A)
   if (tp == 15) return 19;
   return tp != 13 && A.sym_gy % 4 == 0 ? 20 : 16;
 }
-static int march_uniform(const eig_mat_s &A, bool fused = false, i64 nplanes = 0)
+
+// The march variant (march_variants.h) of a launch on A: by image class, the automatic choice or what
+// eig_mat_tune(EIG_TUNE_MARCH_PREFETCH) names, where the image meets that variant's preconditions.
+int march_select(const eig_mat_s &A, bool fused, bool distributed)
 {
-  if (march_kuhn(A)) return kuhn_variant(A);
-  const bool geo2 = A.sym_geo && A.sym_gx % 64 == 0 && A.window * 16 < (i64(1) << 31);
-  if (!A.sym_uniform || (A.kflags & EIG_MAT_NO_UNIFORM))
+  // by tune value; kAuto and every value past a table's end = the automatic choice
+  constexpr int kAuto = -1;
+  constexpr int kUniformGeo2[] = {kAuto, 2, 3, 4, 5, 6, 7, 8, 9}, kUniformGeo[] = {kAuto, 2, 3, 4, 5, 6, 3, 4, 6};
+  constexpr int kValue[] = {kAuto, 0, kAuto, kAuto, kAuto, kAuto, kAuto, kAuto, kAuto, 10,
+                            11,    kAuto, 14, 15, kAuto, 18, 22, 23, 24};
+  const int tp = A.tune_march_prefetch;
+  auto asked = [tp](const auto &table) { return tp >= 0 && tp < (int)std::size(table) ? table[tp] : kAuto; };
+  // whole 64-x runs per wave and 32-bit byte offsets into the pair vectors (geo2 and Kuhn)
+  const bool runs64 = A.sym_gx % 64 == 0 && A.window * 16 < (i64(1) << 31);
+  // the P1 Kuhn 15-point image on one rank; tune value 1 = no Kuhn march
+  if (A.sym_box27 == kKuhn15 && A.sym_nd == 15 && !distributed && runs64 && A.sym_ld * 8 < (i64(1) << 31) && tp != 1)
+    return kuhn_variant(A);
+  const bool geo2 = A.sym_geo && runs64;
+  if (A.sym_uniform && !(A.kflags & EIG_MAT_NO_UNIFORM))
   {
-    if (!geo2 || !march_span1(A) || A.sym_ld * 32 >= (i64(1) << 31) || A.tune_march_prefetch == 1) return 0;
-    // automatic: the fused step on the value pack (15: 223.7 us at 256^3, one rank's 256^2 x 32 slab
-    // 30.4 us; the arrays 226.8 / 31.7), eig_mv / K1 on the plain masked march (0: 152.1 us against 161.4 on
-    // the pack): profiles/r04d_latency.jsonl, r04d_slab.jsonl
-    const int tp = A.tune_march_prefetch;
-    // 22: two grid lines per wave (7-point bands on grids of an even line count)
-    const bool two = A.sym_nd == 7 && A.sym_gy % 2 == 0 && A.sym_gy > 0;
-    if (tp >= 16 && tp <= 18) return two ? tp + 6 : 15;
-    const bool big = A.nb_rows >= EIG_MARCH_2L_MIN_ROWS;
-    return tp == 9 ? 10 : tp == 10 ? 11 : tp == 12 ? 14 : tp == 13 ? 15 : tp == 15 ? 18
-         : fused ? (A.sym_nd == 7 ? (two && big && kMarch2lDefault ? 22 : 15) : 10) : 0;
+    if (!A.sym_geo) return 1;
+    // a geo2 request on a grid that does not qualify takes the march_rows_geo variant with its prefetches.
+    // Automatic (measured: profiles/r03bj_march_variants.jsonl, r03bn_*, r03bp_*; tools/gpu.sh prefetch):
+    // geo2 without prefetch (7) where the grid allows it -- fused step 256^3 125.8 us at 8 plane runs
+    // (plain march 130.0), 128^3 20.1 us (plain 30.2; with the MALL-resident plain stores,
+    // MarchPlan::tstore), one rank's 256^2 x 32 slab 20.5 us (plain 34.5); eig_mv 256^3 46.1 us (plain
+    // 59.4), 128^3 8.0 (12.1).  The prefetching geo2 variants (8, 9) are within a few per cent either
+    // way.  Grids geo2 does not take: march_rows_geo with the +D operand two planes ahead (4).
+    const int v = geo2 ? asked(kUniformGeo2) : asked(kUniformGeo);
+    return v != kAuto ? v : geo2 ? 7 : 4;
   }
-  if (!A.sym_geo) return 1;
-  int u = A.tune_march_prefetch > 0 ? 1 + A.tune_march_prefetch : geo2 ? 7 : 4;
-  if (u >= 7 && !geo2) u = u == 9 ? 6 : u - 4;
-  return u;
+  // value images (EIG_MAT_NO_UNIFORM keeps the array loads): geometric masks only on geo2 grids with
+  // single-offset far spans and a pack descriptor (32 B per row) that fits
+  if (!geo2 || !march_span1(A) || A.sym_ld * 32 >= (i64(1) << 31)) return 0;
+  // two grid lines per wave: 7-point bands on grids of an even line count, else one line of the pack
+  const bool two = A.sym_nd == 7 && A.sym_gy % 2 == 0 && A.sym_gy > 0;
+  const int v = asked(kValue);
+  if (v != kAuto) return march_traits(v).family == kMarchGeo2L2 && !two ? 15 : v;
+  // automatic: the fused step on the value pack (15: 223.7 us at 256^3, one rank's 256^2 x 32 slab
+  // 30.4 us; the arrays 226.8 / 31.7), eig_mv / K1 on the plain masked march (0: 152.1 us against 161.4 on
+  // the pack): profiles/r04d_latency.jsonl, r04d_slab.jsonl; the 2-line march from EIG_MARCH_2L_MIN_ROWS
+  // rows (kMarch2lDefault above)
+  if (!fused) return 0;
+  if (A.sym_nd != 7) return 10;
+  return two && A.nb_rows >= EIG_MARCH_2L_MIN_ROWS && kMarch2lDefault ? 22 : 15;
 }
+static int march_select(const eig_mat_s &A, bool fused) { return march_select(A, fused, A.ctx->distributed()); }
 
+// The variant a launch runs on an image of mode `mode`: a Kuhn variant whatever the mode (its
+// selection tested the image); every other variant needs u8 masks with single-offset far spans,
+// and where the image lacks them the band-array march (variant 0) of its mask width runs.
+static int march_launch_variant(const eig_mat_s &A, int mode, int variant)
+{
+  if (march_traits(variant).family == kMarchKuhn) return variant;
+  return mode == kSymN8 && march_span1(A) ? variant : 0;
+}
+static unsigned march_grid(const MarchPlan &mp) { return (unsigned)((mp.ncol * (i64)mp.nseg + kWaves - 1) / kWaves); }
 
-// Launch a march kernel template KERN<MT, SPAN1> for the image's mask width (u8 masks only can
-// have single-offset far spans).
-#define EIG_MARCH_LAUNCH(KERN, MODE, G, ...)                                                               \
-  do {                                                                                                    \
-    if (mp.uni == 12)                                                                                     \
-      hipLaunchKernelGGL((KERN<uint32_t, false, 12>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);     \
-    else if (mp.uni == 16)                                                                                \
-      hipLaunchKernelGGL((KERN<uint32_t, false, 16>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);     \
-    else if (mp.uni == 20)                                                                                \
-      hipLaunchKernelGGL((KERN<uint32_t, false, 20>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);     \
-    else if (mp.uni == 19)                                                                                \
-      hipLaunchKernelGGL((KERN<uint32_t, false, 19>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);     \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 14)                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 14>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 15)                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 15>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 22)                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 22>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 23)                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 23>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 24)                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 24>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 18)                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 18>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 11)                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 11>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 10)                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 10>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 9)                                      \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 9>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 8)                                 \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 8>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 7)                                 \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 7>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 6)                                 \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 6>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 5)                                 \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 5>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 4)                                 \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 4>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 3)                                 \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 3>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 2)                                 \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 2>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A) && mp.uni == 1)                                 \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 1>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8 && march_span1(A))                                                          \
-      hipLaunchKernelGGL((KERN<uint8_t, true, 0>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);        \
-    else if ((MODE) == kSymN8)                                                                            \
-      hipLaunchKernelGGL((KERN<uint8_t, false, 0>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);       \
-    else                                                                                                  \
-      hipLaunchKernelGGL((KERN<uint32_t, false, 0>), dim3(G), dim3(kStreamThreads), 0, __VA_ARGS__);      \
-  } while (0)
+// Launch the march kernel of plan variant `variant`: calls launch(MT{}, SPAN1, UNI) once, with the
+// template head <MT, SPAN1, UNI> as values (a mask word, a std::bool_constant, a std::integral_constant)
+// -- the head of the variant's traits, or for variant 0 the one of the image's mask width and far
+// spans.  A launcher's generic lambda so instantiates its kernel once per entry of MarchDispatch
+// (variant 0: all three heads).
+template <int... V, class Launch>
+static void march_launch(std::integer_sequence<int, V...>, const eig_mat_s &A, int mode, int variant,
+                         const Launch &launch)
+{
+  const int v = march_launch_variant(A, mode, variant);
+  const bool u8 = mode == kSymN8, span1 = u8 && march_span1(A);
+  auto launch_if = [&](auto vc) {
+    constexpr MarchTraits T = march_traits(decltype(vc)::value);
+    if (v != vc) return false;
+    if constexpr (!T.any_head())
+      launch(std::conditional_t<T.mask_bytes() == 4, uint32_t, uint8_t>{}, std::bool_constant<T.span1()>{}, vc);
+    else if (span1)
+      launch(uint8_t{}, std::true_type{}, vc);
+    else if (u8)
+      launch(uint8_t{}, std::false_type{}, vc);
+    else
+      launch(uint32_t{}, std::false_type{}, vc);
+    return true;
+  };
+  const bool launched = (launch_if(std::integral_constant<int, V>{}) || ...);
+  EIG_CHECK(launched, EIG_ERR_ARG, "march launch: variant without a kernel");
+}
 
 // Plane-marching plan for a whole-matrix launch on the lane-shift band image, or nseg = 0 when the
 // band does not qualify: symmetric offset set with off[0] = -D, off[nd-1] = +D, D a multiple of 64,
@@ -2811,7 +2809,10 @@ static MarchPlan march_plan(const eig_mat_s &A, int mode, i64 zb = 0, i64 ze = -
   MarchPlan mp{};
   if (mode != kSymN8 && mode != kSymN32) return mp;
   i64 D;
-  const bool kuhn = chunk == 64 && march_kuhn(A);
+  const int uni = march_select(A, fused);
+  const MarchTraits T = march_traits(uni);
+  const bool two_lines = T.family == kMarchGeo2L2;
+  const bool kuhn = chunk == 64 && T.family == kMarchKuhn;
   if (!march_enabled(A) || !(kuhn ? (D = (i64)A.sym_gx * A.sym_gy) > 0 : march_geometry(A, D, chunk))) return mp;
   if (ze < 0) ze = (A.nb_rows + D - 1) / D;
   const i64 nplanes = ze - zb;
@@ -2840,41 +2841,29 @@ static MarchPlan march_plan(const eig_mat_s &A, int mode, i64 zb = 0, i64 ze = -
   //    263.2 vs 280.0); not for the 7-point value eig_mv (151.9 vs 154.7 on one box, 152.8 vs 152.2 on
   //    another: r06r_runs_256.jsonl, r06u_runs_uniform_mv.jsonl) nor the uniform-band march (fused
   //    132.7 vs 132.1, eig_mv 61.3 vs 48.9).
-  const int uni = march_uniform(A, fused, nplanes);
-  const bool wide_pack = ncol >= 1024 && chunk == 64 && (kuhn || (fused && (uni == 15 || is_march2l(uni))));
+  const bool wide_pack = ncol >= 1024 && chunk == 64 && T.wide_two && (kuhn || fused);
   if (wide_pack)
     nseg = std::min<i64>(2, nplanes);
   else if (fused && ncol >= 1024)
     nseg = std::min<i64>(nplanes / 2 > 0 ? nplanes / 2 : 1,
-                         std::max<i64>(2, std::min<i64>(uni == 7 || uni >= 10 ? 8 : 6, nplanes / 32)));
+                         std::max<i64>(2, std::min<i64>(T.wide_runs, nplanes / 32)));
   else if (fused)  // (geo2 marches: runs of >= 16 planes -- 128^3 8 runs 24.3 us, 12: 25.3, 16: 26.4)
-    nseg = std::min(nseg, std::max<i64>({1, nplanes / (uni >= 7 ? 16 : 10), (resident / 4 + ncol - 1) / ncol}));
-  // variant 22 marches line PAIRS: half the items per plane run, so twice the runs for as many waves
-  const i64 items_per_run = is_march2l(uni) ? ncol / 2 : ncol;
-  if (is_march2l(uni) && !wide_pack) nseg = std::min<i64>(nplanes, 2 * nseg);
+    nseg = std::min(nseg, std::max<i64>({1, nplanes / (T.geo2_path() ? 16 : 10), (resident / 4 + ncol - 1) / ncol}));
+  // the 2-line variants march line PAIRS: half the items per plane run, so twice the runs for as many waves
+  const i64 items_per_run = two_lines ? ncol / 2 : ncol;
+  if (two_lines && !wide_pack) nseg = std::min<i64>(nplanes, 2 * nseg);
   if (A.tune_march_runs > 0) nseg = std::min<i64>(A.tune_march_runs, nplanes);  // eig_mat_tune
   while (nseg > 1 && (items_per_run * nseg + kWaves - 1) / kWaves > kMaxRedBlocks) --nseg;
   if ((items_per_run * nseg + kWaves - 1) / kWaves > kMaxRedBlocks) return mp;
   mp.D = D;
-  int klo = A.sym_nd, khi = A.sym_nd;
-  for (int k = A.sym_nd - 1; k >= 0; --k)
-  {
-    if (A.sym_off[k] >= -1) klo = k;
-    if (A.sym_off[k] > 1) khi = k;
-  }
+  const auto [klo, khi] = far_spans(A);
   mp.dn = klo > 1 ? A.sym_off[1] : 0;
   mp.Un = A.sym_val + (i64)(klo > 1 ? A.sym_dj[1] : 0) * A.sym_ld;
   mp.dq = khi < A.sym_nd - 1 ? A.sym_off[khi] : 0;
   mp.Uq = A.sym_val + (i64)(khi < A.sym_nd - 1 ? A.sym_dj[khi] : 0) * A.sym_ld;
   for (int q = 0; q < 27; ++q) mp.kj[q] = -1;
-  if (kuhn)
-  {
-    // band array of each upper box offset a D + b nx + c
-    for (int k = 0; k < A.sym_nd; ++k)
-      for (int q = 13; q < 27; ++q)
-        if ((i64)(q / 9 - 1) * D + (i64)((q / 3) % 3 - 1) * A.sym_gx + (q % 3 - 1) == A.sym_off[k])
-          mp.kj[q] = (signed char)A.sym_dj[k];
-  }
+  if (kuhn)  // band array of each upper box offset a D + b nx + c
+    for (int q = 13; q < 27; ++q) mp.kj[q] = (signed char)box_band_array(A, D, q);
   if (A.sym_geo || kuhn)
   {
     mp.gx = A.sym_gx;
@@ -2898,17 +2887,17 @@ static MarchPlan march_plan(const eig_mat_s &A, int mode, i64 zb = 0, i64 ze = -
     mp.cq = khi < A.sym_nd - 1 ? A.sym_uc[A.sym_dj[khi]] : 0.0;
   }
   mp.uni = uni;
-  mp.pack = pack && (uni == 15 || uni == 16 || uni == 18 || uni == 19 || uni == 20 || is_march2l(uni)) ? sym_pack_prepare(A) : nullptr;
+  mp.pack = pack && T.needs_pack() ? sym_pack_prepare(A) : nullptr;
   // measured (tools/march_copy.hip *_pp, profiles/r03bo_march_copy.jsonl): the step's ping-pong at
   // 128^3 (2 x 32 MB of pairs) 12.9 us with plain stores vs 17.6 us nontemporal; at 256^3 (2 x 268
   // MB) no difference either way -- plain stores where every vector a launch touches fits in half
   // of the 256 MB MALL
   // fused step only (eig_mv's y, written repeatedly beside the same x, measured slower: 128^3 9.6 vs
   // 8.0 us)
-  mp.tstore = fused && uni >= 7 && (A.window * 16 * 3 <= (i64(128) << 20) || (A.tune_cache & 1));
+  mp.tstore = fused && T.geo2_path() && (vectors_fit_mall(A) || (A.tune_cache & 1));
   mp.cache = A.tune_cache;
-  // line groups (geo2 value marches 10 / 11 / 14 / 15 on grids of whole 64-x runs and 4-line groups)
-  mp.lines = A.tune_march_lines == 4 && !kuhn && uni >= 10 && uni <= 15 && uni != 12 && mp.gx % 64 == 0 &&
+  // line groups (MarchTraits::line_groups, on grids of whole 64-x runs and 4-line groups)
+  mp.lines = A.tune_march_lines == 4 && T.line_groups && mp.gx % 64 == 0 &&
                      mp.gx > 0 && mp.gy % 4 == 0 && (i64)mp.gx * mp.gy == D
                  ? 4
                  : 0;
@@ -2973,11 +2962,13 @@ void launch_spmv(const eig_mat_s &A, const double *x, double *y, const i32 *slic
     MarchPlan mp = launch_plan(A, mode, slices, first, count);
     // keep: y is read by the very next launch (the pipelined step's S) -- plain stores on grids
     // whose vectors fit the MALL, as the fused step's (MarchPlan::tstore)
-    if (keep && mp.uni >= 7 && A.window * 16 * 3 <= (i64(128) << 20)) mp.tstore = 1;
+    if (keep && march_traits(mp.uni).geo2_path() && vectors_fit_mall(A)) mp.tstore = 1;
     if (mp.nseg > 0)
     {
-      const unsigned G = (unsigned)((mp.ncol * (i64)mp.nseg + kWaves - 1) / kWaves);
-      EIG_MARCH_LAUNCH(k_spmv_march, mode, G, s, A.nb_rows, A.own_offset, sell_b1(A), mp, x, y);
+      march_launch(MarchDispatch{}, A, mode, mp.uni, [&](auto mt, auto span1, auto uni) {
+        hipLaunchKernelGGL((k_spmv_march<decltype(mt), span1(), uni()>), dim3(march_grid(mp)), dim3(kStreamThreads), 0,
+                           s, A.nb_rows, A.own_offset, sell_b1(A), mp, x, y);
+      });
       return;
     }
   }
@@ -3038,9 +3029,11 @@ void launch_lanczos_spmv(const eig_mat_s &A, const double *u, const double *up, 
     const MarchPlan mp = launch_plan(A, mode, slices, first, count);
     if (mp.nseg > 0)
     {
-      const unsigned G = (unsigned)((mp.ncol * (i64)mp.nseg + kWaves - 1) / kWaves);
-      EIG_MARCH_LAUNCH(k_lanczos_spmv_march, mode, G, s, A.nb_rows, A.own_offset, sell_b1(A), mp, u, up, t, j,
-                       st.nsum, dot_out, beta_out, red.partials, red.ticket(ticket));
+      march_launch(MarchDispatch{}, A, mode, mp.uni, [&](auto mt, auto span1, auto uni) {
+        hipLaunchKernelGGL((k_lanczos_spmv_march<decltype(mt), span1(), uni()>), dim3(march_grid(mp)),
+                           dim3(kStreamThreads), 0, s, A.nb_rows, A.own_offset, sell_b1(A), mp, u, up, t, j, st.nsum,
+                           dot_out, beta_out, red.partials, red.ticket(ticket));
+      });
       return;
     }
   }
@@ -3084,10 +3077,12 @@ void launch_lanczos_fused(const eig_mat_s &A, const double *P, double *Pout, con
     const MarchPlan mp = launch_plan(A, mode, slices, first, count, true);
     if (mp.nseg > 0)
     {
-      const unsigned G = (unsigned)((mp.ncol * (i64)mp.nseg + kWaves - 1) / kWaves);
-      EIG_MARCH_LAUNCH(k_lanczos_fused_march, mode, G, s, A.nb_rows, A.own_offset, sell_b1(A), mp,
-                       reinterpret_cast<const dpair *>(P), reinterpret_cast<dpair *>(Pout), fa, out, red.partials,
-                       red.ticket(ticket));
+      march_launch(MarchDispatch{}, A, mode, mp.uni, [&](auto mt, auto span1, auto uni) {
+        hipLaunchKernelGGL((k_lanczos_fused_march<decltype(mt), span1(), uni()>), dim3(march_grid(mp)),
+                           dim3(kStreamThreads), 0, s, A.nb_rows, A.own_offset, sell_b1(A), mp,
+                           reinterpret_cast<const dpair *>(P), reinterpret_cast<dpair *>(Pout), fa, out, red.partials,
+                           red.ticket(ticket));
+      });
       return;
     }
   }
@@ -3152,12 +3147,7 @@ static bool gspans(const eig_mat_s &A, i64 &P, GSpans &sp)
     return -1;
   };
   if (kof(1) < 0 || kof(-1) < 0) return false;
-  int klo = nd, khi = nd;
-  for (int k = nd - 1; k >= 0; --k)
-  {
-    if (A.sym_off[k] >= -1) klo = k;
-    if (A.sym_off[k] > 1) khi = k;
-  }
+  const auto [klo, khi] = far_spans(A);
   // candidates for P from the widest down; the first whose four spans fit
   for (int kp = nd - 1; kp >= khi; --kp)
   {
@@ -3204,7 +3194,7 @@ static bool launch_marchg(const eig_mat_s &A, i64 m, const double *X, double *Y,
   mp.mrows = A.nslices * 64;
   mp.ncol = (int)ncol;
   mp.nseg = (int)nseg;
-  const dim3 grid((unsigned)((ncol * mp.nseg + kWaves - 1) / kWaves), (unsigned)(m / 8));
+  const dim3 grid(march_grid(mp), (unsigned)(m / 8));
   if (mode == kSymN8)
     hipLaunchKernelGGL((k_spmm8_marchg<uint8_t, EPI>), grid, dim3(kStreamThreads), 0, s, A.nb_rows, A.own_offset,
                        A.window, sell_b1(A), mp, sp, X, Y, Bv, dinv, omega, gamma);
@@ -3226,8 +3216,7 @@ bool launch_spmm_march(const eig_mat_s &A, i64 m, const double *X, double *Y, hi
   const int mode = image_mode(A);
   const MarchPlan mp = march_plan(A, mode, 0, -1, false, 16);
   if (mp.nseg == 0) return launch_marchg<kGStore>(A, m, X, Y, nullptr, nullptr, 0.0, 0.0, s);
-  const i64 items = mp.ncol * (i64)mp.nseg;
-  const dim3 grid((unsigned)((items + kWaves - 1) / kWaves), (unsigned)(m / 8));
+  const dim3 grid(march_grid(mp), (unsigned)(m / 8));
   if (mode == kSymN8)
     hipLaunchKernelGGL((k_spmm8_march<uint8_t>), grid, dim3(kStreamThreads), 0, s, A.nb_rows, A.own_offset, A.window,
                        sell_b1(A), mp, X, Y);
@@ -3247,8 +3236,7 @@ bool launch_spmm_march_dot(const eig_mat_s &A, i64 m, const double *X, double *Y
   if (!is_sym_mode(mode)) return false;
   const MarchPlan mp = march_plan(A, mode, 0, -1, false, 16);
   if (mp.nseg == 0) return false;
-  const i64 items = mp.ncol * (i64)mp.nseg;
-  const dim3 grid((unsigned)((items + kWaves - 1) / kWaves), (unsigned)(m / 8));
+  const dim3 grid(march_grid(mp), (unsigned)(m / 8));
   if ((i64)grid.x * 8 * grid.y > (i64)kMaxRedBlocks * kMaxRedVals || grid.y > (unsigned)kNumTickets) return false;
   if (mode == kSymN8)
     hipLaunchKernelGGL((k_spmm8_march<uint8_t, true>), grid, dim3(kStreamThreads), 0, s, A.nb_rows, A.own_offset,
@@ -3268,8 +3256,7 @@ bool launch_spmm_march_dot_gram(const eig_mat_s &A, i64 m, const double *X, doub
   if (!is_sym_mode(mode)) return false;
   const MarchPlan mp = march_plan(A, mode, 0, -1, false, 16);
   if (mp.nseg == 0) return false;
-  const i64 items = mp.ncol * (i64)mp.nseg;
-  const dim3 grid((unsigned)((items + kWaves - 1) / kWaves), 1u);
+  const dim3 grid(march_grid(mp), 1u);
   if ((i64)grid.x * 72 + 8 * 72 > (i64)kMaxRedBlocks * kMaxRedVals) return false;
   if (mode == kSymN8)
     hipLaunchKernelGGL((k_spmm8_march<uint8_t, 2>), grid, dim3(kStreamThreads), 0, s, A.nb_rows, A.own_offset,
@@ -3291,13 +3278,13 @@ void lanczos_kernel_info(const eig_mat_s &A, bool fused, std::string &name, i64 
     const bool whole = !A.ctx->distributed() || (A.recvs.empty() && A.sends.empty());
     const bool march = whole ? (march_plan(A, mode).nseg > 0)
                              : march_split_active(A);
-    // the uniform-band march streams the row mask and the vectors only; the value march (10, 11)
-    // the band arrays and the vectors (geometric masks: no mask stream)
-    const int mv = march && ((mode == kSymN8 && march_span1(A)) || march_kuhn(A)) ? march_uniform(A, fused) : 0;
-    if (mv >= 10)
-      bytes = 8 * (mv == 15 || mv == 18 || is_march2l(mv) ? 4 : (i64)A.sym_nup) * n + vec;
-    else if (mv)
-      bytes = (mv >= 2 ? 0 : (i64)A.sym_mask_bytes * n) + vec;
+    // the march streams the band arrays its variant reads (uniform values: none; the 7-point pack: 4),
+    // the row mask unless it comes from the coordinates, and the vectors
+    if (march)
+    {
+      const MarchTraits T = march_traits(march_launch_variant(A, mode, march_select(A, fused)));
+      bytes = 8 * (i64)T.stream_arrays(A.sym_nup) * n + (T.geo_masks ? 0 : (i64)A.sym_mask_bytes * n) + vec;
+    }
     name = fused ? (march ? "k_lanczos_fused_march" : "k_lanczos_fused_b1")
                  : (march ? "k_lanczos_spmv_march" : "k_lanczos_spmv_b1");
   }

@@ -219,10 +219,15 @@ typedef struct eig_mat_info {
                              neighbours (geometric row masks; a property of the pattern, any values) */
   int64_t march_variant;  /* plane-march variant of a whole-matrix fused Lanczos launch (-1: no
                              march, the row kernels): 0 band arrays + loaded masks, 1 uniform values +
-                             loaded masks, 2..9 uniform values + geometric masks, 10 / 11 band arrays
-                             streamed + geometric masks (the value march; 11 one plane ahead, 14 / 15
-                             through global addresses, 15 on a pair-packed copy of the arrays), 12 / 16
-                             the P1 Kuhn 15-point box march (16 on its pair-packed values) */
+                             loaded masks, 2..9 uniform values + geometric masks (3..6 the +D operand
+                             prefetched, 7..9 without masks or selects), 10 / 11 / 14 band arrays
+                             streamed + geometric masks (the value march; 11 one plane ahead, 14
+                             through global addresses), 15 / 18 the value march on a pair-packed copy
+                             of the arrays (18: built for 7 waves per SIMD), 22 / 23 / 24 that pack
+                             marched two grid lines per wave (5 / 4 / 6 waves per SIMD), 12 / 16 / 19 /
+                             20 the P1 Kuhn 15-point box march (12 band arrays, 16 / 19 its pair-packed
+                             values at 4 / 5 waves per SIMD, 20 the pack with the line exchange in
+                             LDS); 13, 17 and 21 are unused */
   int64_t march_variant_mv; /* the same for eig_mv (BCRSMatrix::mv) */
 } eig_mat_info;
 int eig_mat_get_info(eig_mat_t mat, eig_mat_info *info);
@@ -275,11 +280,14 @@ enum { EIG_TUNE_MARCH_RUNS = 1, EIG_TUNE_BOX_SEGS = 2, EIG_TUNE_MARCH_PREFETCH =
 /* EIG_TUNE_MARCH_PREFETCH (geometric uniform-band images, eig_mat_info.sym_uniform = 2): 1 = the
  * plain march, 2 / 3 / 4 = the +D operand loaded 1 / 2 / 3 planes ahead, 5 = 3 planes ahead and the
  * neighbour gathers 1 plane ahead; 6 / 7 / 8 = the variants of 2 / 3 / 5 without row masks or
- * selects (missing neighbours read as exact zeros; grids whose x extent is a multiple of 64);
+ * selects (missing neighbours read as exact zeros; grids whose x extent is a multiple of 64; other
+ * grids take the variants of 2 / 3 / 5); every other value = automatic;
  * on geometric bands whose values are not uniform (or EIG_MAT_NO_UNIFORM): 1 = the plain masked
  * march on the band arrays, 9 = the value march (eig_mat_info.march_variant 10: the band arrays
  * streamed, masks from the coordinates), 10 = the same with the value streams one plane ahead (11),
- * 11 = the value march on a packed copy of the 4 arrays (13: {+D, 0, +1, +nx} per row, two 16-B loads);
+ * 12 = the value march through global addresses (14), 13 = the value march on a packed copy of the 4
+ * arrays (15: {+D, 0, +1, +nx} per row, two 16-B loads), 15 = the same built for 7 waves per SIMD (18);
+ * 11 and 14 select nothing (automatic);
  * 16 / 17 / 18 = that pack marched TWO grid lines per wave (march variants 22 / 23 / 24: 5 / 4 / 6
  * waves per SIMD; 7-point bands, an even line count) -- the +-nx neighbours across the pair from
  * registers, half the gathers; the fused step's sums then add the rows in another order;

@@ -1,5 +1,7 @@
-"""Host-side unit check of the march-variant selection (tests/cpp/march_select_test.cc): the P1 Kuhn
-value-pack marches must not be chosen where their 32-bit buffer descriptor would wrap."""
+"""Host-side unit check of the march-variant table and selection (tests/cpp/march_select_test.cc): the
+traits of every variant, the variant march_select returns for every image class and tune value, and
+that the P1 Kuhn value-pack marches are not chosen where their 32-bit buffer descriptor would wrap
+(ADVICE r4)."""
 import os
 import subprocess
 
