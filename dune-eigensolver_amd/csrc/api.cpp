@@ -2008,10 +2008,26 @@ extern "C" int eig_spmm_mv8(eig_mat_t A, int64_t m, const double *Qin, double *Q
   return guard(A ? A->ctx : nullptr, [&] {
     EIG_CHECK(A && Qin && Qout, EIG_ERR_ARG, "eig_spmm_mv8: null argument");
     EIG_MV8_CHECK(m);
+    // the reference's entry point keeps the reference's refusal; blocks go through eig_spmm_blk_mv8
+    EIG_CHECK(A->br == 1 && A->bc == 1, EIG_ERR_BLOCKSIZE,
+              "matmul_sparse_tallskinny_blocked: only implemented for FieldMatrix<..,1,1>");
     EIG_CHECK(A->nb_rows == A->nb_cols && !A->ctx->distributed(), EIG_ERR_SHAPE,
               "eig_spmm_mv8: square single-rank matrix required");
     DeviceGuard dg(A->ctx->device);
     if (m > 0) launch_spmm_mv8(*A, m, Qin, Qout, A->ctx->stream);
+  });
+}
+
+extern "C" int eig_spmm_blk_mv8(eig_mat_t A, int64_t m, const double *Qin, double *Qout)
+{
+  return guard(A ? A->ctx : nullptr, [&] {
+    EIG_CHECK(A && Qin && Qout && Qin != Qout, EIG_ERR_ARG, "eig_spmm_blk_mv8: null or aliased argument");
+    EIG_MV8_CHECK(m);
+    EIG_CHECK(A->br == A->bc, EIG_ERR_BLOCKSIZE, "eig_spmm_blk_mv8: blocks of input matrix must be square");
+    EIG_CHECK(A->nb_rows == A->nb_cols && !A->ctx->distributed(), EIG_ERR_SHAPE,
+              "eig_spmm_blk_mv8: square single-rank matrix required");
+    DeviceGuard dg(A->ctx->device);
+    if (m > 0) launch_spmm_mv8(*A, m, Qin, Qout, A->ctx->stream);  // 1x1: the eig_spmm_mv8 kernels
   });
 }
 
@@ -2060,7 +2076,7 @@ void spmm_dot_gram_device(const eig_mat_s &A, const double *X, double *Y, double
   if (launch_spmm_dot_gram_mv8(A, 8, X, Y, dp, gram, ctx->stream, ctx->red)) return;
   // no fused kernel on this image: the product with its dots, then the panel Gram of the block
   launch_spmm_dot_mv8(A, 8, X, Y, dp, ctx->stream, ctx->red);
-  gram_device(ctx, A.nb_rows, 8, 8, Y, Y, gram);
+  gram_device(ctx, A.nb_rows * A.br, 8, 8, Y, Y, gram);  // scalar rows
 }
 
 void orthonormalize_device(eig_ctx_t ctx, i64 n, i64 m, double *Q, int variant, const double *gram0)

@@ -196,10 +196,13 @@ void random_block(eig_ctx_t ctx, i64 n, i64 m, unsigned seed, double *Q)
   EIG_HIP(hipStreamSynchronize(ctx->stream));
 }
 
-void check_inverse_matrix(const eig_mat_s *A, const char *who)
+// blocks: the caller runs on square blocks 1..4 (StandardInverse, the symmetric shift-invert
+// drivers); the others keep the reference's FieldMatrix<..,1,1> restriction
+void check_inverse_matrix(const eig_mat_s *A, const char *who, bool blocks = false)
 {
   EIG_CHECK(A->br == A->bc, EIG_ERR_ARG, std::string(who) + ": blocks of input matrix must be square");
-  EIG_CHECK(A->br == 1, EIG_ERR_BLOCKSIZE, "matmul_sparse_tallskinny_blocked: only implemented for FieldMatrix<..,1,1>");
+  EIG_CHECK(blocks || A->br == 1, EIG_ERR_BLOCKSIZE,
+            "matmul_sparse_tallskinny_blocked: only implemented for FieldMatrix<..,1,1>");
   EIG_CHECK(!distributed(*A), EIG_ERR_ARG, std::string(who) + ": single rank only");
   EIG_CHECK(A->nb_rows == A->nb_cols, EIG_ERR_SHAPE, std::string(who) + ": square matrix required");
 }
@@ -211,11 +214,11 @@ extern "C" int eig_standard_inverse(eig_mat_t A, eig_lu_t lu, double shift, doub
 {
   return guard(A ? A->ctx : nullptr, [&] {
     EIG_CHECK(A && eval_host && nev > 0, EIG_ERR_ARG, "eig_standard_inverse: bad argument");
-    check_inverse_matrix(A, "StandardInverse");
+    check_inverse_matrix(A, "StandardInverse", true);
     eig_ctx_t ctx = A->ctx;
     EIG_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const i64 n = A->nb_rows;
+    const i64 n = A->nb_rows * A->br;  // scalar rows
     const i64 m = (nev / 8 + std::min(nev % 8, 1)) * 8;  // eigensolver.hh:133
     // basis ping-pong B[0] / B[1] and a product block Z: iteration k solves from B[(k - 1) % 2] into
     // B[k % 2], so the queued iteration k + 1 never touches iteration k's basis (look-ahead over the
@@ -393,7 +396,9 @@ void shifted_copy(eig_mat_s &A, eig_mat_s *B, double sigma, std::vector<i64> &rp
 {
   mat_download_bcsr(A, rp, c, v);
   if (sigma == 0.0) return;
+  // block rows; a stored block is b x b values, row-major, at v[q * bb] (b = 1: the scalar entry)
   const i64 n = A.nb_rows;
+  const int b = A.br, bb = b * b;
   if (!B)
   {
     for (i64 i = 0; i < n; ++i)
@@ -401,7 +406,8 @@ void shifted_copy(eig_mat_s &A, eig_mat_s *B, double sigma, std::vector<i64> &rp
       const i32 *b0 = c.data() + rp[i], *b1 = c.data() + rp[i + 1];
       const i32 *hit = std::lower_bound(b0, b1, (i32)i);
       EIG_CHECK(hit != b1 && *hit == (i32)i, EIG_ERR_SHAPE, "shift-invert: A has no diagonal entry");
-      v[hit - c.data()] -= sigma;
+      // the identity's block: sigma off the diagonal entries of the diagonal block
+      for (int d = 0; d < b; ++d) v[(size_t)(hit - c.data()) * bb + d * b + d] -= sigma;
     }
     return;
   }
@@ -415,7 +421,7 @@ void shifted_copy(eig_mat_s &A, eig_mat_s *B, double sigma, std::vector<i64> &rp
       const i32 *b0 = c.data() + rp[i], *b1 = c.data() + rp[i + 1];
       const i32 *hit = std::lower_bound(b0, b1, bc[q]);
       EIG_CHECK(hit != b1 && *hit == bc[q], EIG_ERR_SHAPE, "shift-invert: pattern(B) must be contained in pattern(A)");
-      v[hit - c.data()] -= sigma * bv[q];
+      for (int t = 0; t < bb; ++t) v[(size_t)(hit - c.data()) * bb + t] -= sigma * bv[(size_t)q * bb + t];
     }
 }
 
@@ -423,12 +429,15 @@ void shifted_copy(eig_mat_s &A, eig_mat_s *B, double sigma, std::vector<i64> &rp
 
 namespace {
 
-void shift_invert_check(eig_mat_t A, eig_mat_t B)
+// blocks: square blocks 1..4 (the symmetric driver, like the reference's, needs only mv and the
+// factorisation); B then has A's block size
+void shift_invert_check(eig_mat_t A, eig_mat_t B, bool blocks = false)
 {
-  check_inverse_matrix(A, "computeGenSymShiftInvertMinMagnitude");
+  check_inverse_matrix(A, "computeGenSymShiftInvertMinMagnitude", blocks);
   if (B)
   {
-    check_inverse_matrix(B, "computeGenSymShiftInvertMinMagnitude");
+    check_inverse_matrix(B, "computeGenSymShiftInvertMinMagnitude", blocks);
+    EIG_CHECK(B->br == A->br, EIG_ERR_BLOCKSIZE, "shift-invert: A and B block sizes differ");
     EIG_CHECK(B->ctx == A->ctx && B->nb_rows == A->nb_rows, EIG_ERR_SHAPE, "shift-invert: A and B sizes differ");
   }
 }
@@ -447,7 +456,7 @@ void shift_invert_factor(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma, Lu
     shifted_copy(*A, B, sigma, rp, c, v);
     factor_host(*A, rp, c, v, F);
   }
-  EIG_CHECK(lu_size(F.lu) == A->nb_rows, EIG_ERR_SHAPE, "shift-invert: factorisation size differs from A");
+  EIG_CHECK(lu_size(F.lu) == A->nb_rows * A->br, EIG_ERR_SHAPE, "shift-invert: factorisation size differs from A");
 }
 
 // One computeGenSymShiftInvertMinMagnitude solve (ARSymGenEig 'S' mode, "LM") with the factors F.
@@ -457,7 +466,7 @@ void shift_invert_core(eig_mat_t A, eig_mat_t B, const LuRef &F, double sigma, i
     eig_ctx_t ctx = A->ctx;
     EIG_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const i64 n = A->nb_rows;
+    const i64 n = A->nb_rows * A->br;  // scalar rows (square blocks 1..4: only mv and the factors are used)
     if (ncv <= 0) ncv = (int)std::min<i64>(n, std::max(2 * nev + 1, 20));  // ARPACK++ ncv = 0 (auto)
     EIG_CHECK(nev < ncv && ncv <= n && ncv <= 500, EIG_ERR_ARG, "shift-invert: need nev < ncv <= min(n, 500)");
     if (tol <= 0.0) tol = 2.220446049250313e-16;  // tol = 0: machine precision (ARPACK)
@@ -891,6 +900,15 @@ bool si_use_block(i64 n, int nev, int ncv, int flags)
 void shift_invert_run(eig_mat_t A, eig_mat_t B, const LuRef &F, double sigma, int nev, int ncv, double tol, int maxit,
                       unsigned seed, double *eval_host, double *evec_host, int *restarts, int flags)
 {
+  if (A->br > 1)
+  {
+    // blocked matrices: the one-vector method (mv and the factors only); the block method's panel
+    // kernels are FieldMatrix<..,1,1> code
+    EIG_CHECK(!(flags & EIG_SI_BLOCK), EIG_ERR_BLOCKSIZE,
+              "shift-invert (block): only implemented for FieldMatrix<..,1,1> (use EIG_SI_AUTO / EIG_SI_SINGLE)");
+    shift_invert_core(A, B, F, sigma, nev, ncv, tol, maxit, seed, eval_host, evec_host, restarts);
+    return;
+  }
   if (si_use_block(A->nb_rows, nev, ncv, flags))
     shift_invert_block_core(A, B, F, sigma, nev, ncv, tol, maxit, seed, eval_host, evec_host, restarts);
   else
@@ -907,7 +925,9 @@ extern "C" int eig_shift_invert_solve_ex(eig_mat_t A, eig_mat_t B, eig_lu_t lu, 
     EIG_CHECK(A && eval_host && nev > 0, EIG_ERR_ARG, "eig_shift_invert_solve: bad argument");
     EIG_CHECK((flags & ~(EIG_SI_SINGLE | EIG_SI_BLOCK)) == 0 && flags != (EIG_SI_SINGLE | EIG_SI_BLOCK), EIG_ERR_ARG,
               "eig_shift_invert_solve_ex: unknown flags");
-    shift_invert_check(A, B);
+    shift_invert_check(A, B, true);
+    EIG_CHECK(A->br == 1 || !(flags & EIG_SI_BLOCK), EIG_ERR_BLOCKSIZE,
+              "shift-invert (block): only implemented for FieldMatrix<..,1,1> (use EIG_SI_AUTO / EIG_SI_SINGLE)");
     EIG_HIP(hipSetDevice(A->ctx->device));
     LuRef F;
     shift_invert_factor(A, B, lu, sigma, F);
@@ -937,7 +957,7 @@ extern "C" int eig_shift_invert_adaptive(eig_mat_t A, eig_mat_t B, eig_lu_t lu, 
               "eig_shift_invert_adaptive: bad argument");
     // (arpack_geneo_wrapper.hh:693-694: "initial_nev too large")
     EIG_CHECK(initial_nev <= max_nev, EIG_ERR_ARG, "eig_shift_invert_adaptive: initial_nev too large");
-    shift_invert_check(A, B);
+    shift_invert_check(A, B, true);
     EIG_HIP(hipSetDevice(A->ctx->device));
     LuRef F;
     shift_invert_factor(A, B, lu, sigma, F);

@@ -74,11 +74,152 @@ __global__ __launch_bounds__(256) void k_spmm_mv8(i64 nrows, i64 nslices, const 
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// a2 on square B x B blocks (B = 2, 3, 4; the reference throws "only implemented for
+// FieldMatrix<..,1,1>" here): Qout = A Qin over the blocked SELL-64 image (internal.h: block column
+// of entry k of slice row r at slice_ptr[s] + k*64 + r, value t = r_blk*B + c_blk at
+// (slice_ptr[s] + k*64)*B*B + t*64 + r, padding col < 0).  Qin / Qout have n = nbrows*B scalar rows;
+// block row I, component r is scalar row I*B + r.
+// Mapping as k_spmm_mv8: a workgroup (4 waves) takes one 64-block-row slice at a time, lane L of
+// wave w owns block row 16 w + L/4 and the column pair 2 (L%4), 2 (L%4)+1 of up to MB column blocks
+// (B*MB double2 accumulators), so a slice's values are read once per MB column blocks.  The matrix
+// stream (columns, values) is read once per workgroup row: nontemporal loads, the next block column
+// fetched one entry ahead.  The B Qin rows of a block column are contiguous (B*64 B per column
+// block), read as 16 B per lane.
+// Arithmetic per scalar row and column: s = 0; over the stored blocks in stored order, over
+// c = 0..B-1: s += a[r][c] * x[col*B + c] (products and sums rounded separately) -- the order of
+// k_spmv_blk, and of the 1x1 product on the matrix's scalar expansion, so the result is bitwise both.
+// ---------------------------------------------------------------------------------------------
+template <int B, int MB>
+__global__ __launch_bounds__(256) void k_spmm_blk_mv8(i64 nbrows, i64 nslices, const i64 *__restrict__ slice_ptr,
+                                                      const double *__restrict__ val, const i32 *__restrict__ col,
+                                                      const double *__restrict__ Qin, double *__restrict__ Qout, i64 n,
+                                                      int nblk_total, int xcd_map)
+{
+  constexpr int BB = B * B;
+  const int wave = threadIdx.x >> 6, L = threadIdx.x & 63;
+  const int cp = L & 3;
+  const int ri = wave * 16 + (L >> 2);
+  const int b0 = blockIdx.y * MB;
+  // slice schedule.  xcd_map (gridDim.x a multiple of 8): the slices are cut into 8 contiguous
+  // shares and the workgroups with blockIdx.x % 8 == x -- dealt to XCD x (round-robin dispatch: a
+  // speed assumption only, as k_sell_mv8q's) -- walk share x, so the Qin rows an XCD's resident
+  // workgroups gather are one neighbourhood of the matrix, not the whole front of the grid, and stay
+  // in its own L2.  Otherwise the plain grid stride.
+  const i64 share = xcd_map ? (nslices + 7) / 8 : nslices;
+  const i64 s0 = xcd_map ? (blockIdx.x & 7) * share + (blockIdx.x >> 3) : blockIdx.x;
+  const i64 s1 = xcd_map ? min(nslices, ((blockIdx.x & 7) + 1) * share) : nslices;
+  const i64 step = xcd_map ? gridDim.x >> 3 : gridDim.x;
+  for (i64 s = s0; s < s1; s += step)
+  {
+    const i64 base = slice_ptr[s];
+    const int width = (int)((slice_ptr[s + 1] - base) >> 6);
+    double2 acc[MB][B];
+#pragma unroll
+    for (int q = 0; q < MB; ++q)
+#pragma unroll
+      for (int r = 0; r < B; ++r) acc[q][r] = make_double2(0.0, 0.0);
+    i32 c = width > 0 ? __builtin_nontemporal_load(col + base + ri) : -1;
+    for (int k = 0; k < width; ++k)
+    {
+      const i32 cn = k + 1 < width ? __builtin_nontemporal_load(col + base + (i64)(k + 1) * 64 + ri) : -1;
+      if (c >= 0)
+      {
+        const double *vb = val + (base + (i64)k * 64) * BB + ri;
+        double a[BB];
+#pragma unroll
+        for (int t = 0; t < BB; ++t) a[t] = __builtin_nontemporal_load(vb + t * 64);
+#pragma unroll
+        for (int q = 0; q < MB; ++q)
+        {
+          if (b0 + q < nblk_total)
+          {
+            const double2 *xr = reinterpret_cast<const double2 *>(Qin + ((i64)(b0 + q) * n + (i64)c * B) * 8) + cp;
+            double2 xv[B];
+#pragma unroll
+            for (int cc = 0; cc < B; ++cc) xv[cc] = xr[cc * 4];
+#pragma unroll
+            for (int r = 0; r < B; ++r)
+            {
+              double2 sacc = acc[q][r];
+#pragma unroll
+              for (int cc = 0; cc < B; ++cc)
+              {
+                sacc.x += a[r * B + cc] * xv[cc].x;
+                sacc.y += a[r * B + cc] * xv[cc].y;
+              }
+              acc[q][r] = sacc;
+            }
+          }
+        }
+      }
+      c = cn;
+    }
+    const i64 row = s * 64 + ri;
+    if (row < nbrows)
+    {
+#pragma unroll
+      for (int q = 0; q < MB; ++q)
+        if (b0 + q < nblk_total)
+        {
+          double2 *yr = reinterpret_cast<double2 *>(Qout + ((i64)(b0 + q) * n + row * B) * 8) + cp;
+#pragma unroll
+          for (int r = 0; r < B; ++r) yr[r * 4] = acc[q][r];
+        }
+    }
+  }
+}
+
+// column blocks per workgroup of k_spmm_blk_mv8<B, .>: the most that keep the kernel at 4 waves per
+// SIMD (<= 128 VGPRs) without scratch (DESIGN.md "Blocked SpMM")
+template <int B>
+constexpr int spmm_blk_mb()
+{
+  return B == 4 ? 2 : 4;
+}
+
+template <int B, int MB>
+static void launch_spmm_blk_mb(const eig_mat_s &A, int nblk, const double *Qin, double *Qout, hipStream_t s)
+{
+  const int gy = (nblk + MB - 1) / MB;
+  static const bool flat = std::getenv("EIGMI_SPMM_BLK_FLAT") != nullptr;  // A/B: the plain grid stride
+  // XCD shares need a grid of whole groups of 8 and at least a slice per workgroup
+  const bool xcd = !flat && A.nslices >= 64;
+  int gx = grid_for(A.nslices, 1, kStreamBlocks);
+  if (xcd) gx = std::min(kStreamBlocks, (gx + 7) / 8 * 8);
+  hipLaunchKernelGGL((k_spmm_blk_mv8<B, MB>), dim3(gx, gy), dim3(256), 0, s, A.nb_rows, A.nslices, A.slice_ptr, A.val,
+                     A.col, Qin, Qout, A.nb_rows * B, nblk, xcd ? 1 : 0);
+}
+
+// One instantiation per block size, also for a narrow product: instantiations with 1 / 2 column
+// blocks (72 / 98 VGPRs at B = 3, 7 / 4 waves per SIMD) ran m = 8 at the same 240-250 us as this one
+// in a same-run A/B (DESIGN.md "Blocked SpMM": the kernel is bound by its memory-instruction rate,
+// not by the waves in flight).
+template <int B>
+static void launch_spmm_blk(const eig_mat_s &A, int nblk, const double *Qin, double *Qout, hipStream_t s)
+{
+  launch_spmm_blk_mb<B, spmm_blk_mb<B>()>(A, nblk, Qin, Qout, s);
+}
+
 void launch_spmm_mv8(const eig_mat_s &A, i64 m, const double *Qin, double *Qout, hipStream_t s)
 {
-  EIG_CHECK(A.br == 1 && A.bc == 1, EIG_ERR_BLOCKSIZE,
-            "matmul_sparse_tallskinny_blocked: only implemented for FieldMatrix<..,1,1>");
   const int nblk = (int)(m / 8);
+  if (A.br == A.bc && A.br > 1)
+  {
+    // square blocks: the blocked image (R = 1), one rank, columns index Qin's scalar rows directly
+    EIG_CHECK(!A.ctx->distributed(), EIG_ERR_ARG, "blocked SpMM: single rank only");
+    EIG_CHECK(A.R == 1 && A.nb_rows == A.nb_cols, EIG_ERR_SHAPE, "blocked SpMM: square matrix required");
+    if (nblk <= 0 || A.nb_rows <= 0) return;
+    switch (A.br)
+    {
+      case 2: launch_spmm_blk<2>(A, nblk, Qin, Qout, s); return;
+      case 3: launch_spmm_blk<3>(A, nblk, Qin, Qout, s); return;
+      case 4: launch_spmm_blk<4>(A, nblk, Qin, Qout, s); return;
+      default: break;
+    }
+  }
+  EIG_CHECK(A.br == 1 && A.bc == 1, EIG_ERR_BLOCKSIZE,
+            "matmul_sparse_tallskinny_blocked: only implemented for FieldMatrix<..,1,1> and square blocks 2..4");
   if (A.R == 1)
   {
     // row per lane over 64-row slices, window layout (k_block.hip); ld = n on one rank
@@ -104,7 +245,7 @@ void launch_spmm_dot_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, 
     if (!box_spmm_applies(A, m) && launch_spmm_march_dot(A, m, X, Y, dp, red, s)) return;
   }
   launch_spmm_mv8(A, m, X, Y, s);
-  launch_dot_diag_mv8(A.nb_rows, m, X, Y, dp, 0, s, red);
+  launch_dot_diag_mv8(A.nb_rows * A.br, m, X, Y, dp, 0, s, red);  // scalar rows
 }
 
 bool launch_spmm_dot_gram_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, double *dp, double *gram,

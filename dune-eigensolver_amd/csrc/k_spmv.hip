@@ -3334,7 +3334,7 @@ std::string kernel_for(const eig_mat_s &A, int op)
       // 3-D box stencils whose rows are class-constant: the row-class kernels for any m % 8 == 0
       if (b1 && box_prepare(A) && A.box_ctab) return op == 3 ? "k_boxc_mv8" : "k_boxc_mv8_cheb";
     {
-      if (!b1) return "none";
+      if (!b1) return (op == 3 && A.br == A.bc) ? "k_spmm_blk_mv8" : "none";  // square blocks 2..4 (k_mv8.hip)
       i64 P;
       GSpans sp;
       const bool g = marchg_enabled(A) && (mode == kSymN8 || mode == kSymN32) && gspans(A, P, sp) &&

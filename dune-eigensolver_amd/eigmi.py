@@ -159,6 +159,7 @@ SIGNATURES = {
     "eig_orthonormalize_gram_mv8": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "eig_stream_copy_timed": (_int, [_vp, _i64, _vp, _vp, _int, _int, ctypes.POINTER(_dbl)]),
     "eig_spmm_mv8": (_int, [_vp, _i64, _vp, _vp]),
+    "eig_spmm_blk_mv8": (_int, [_vp, _i64, _vp, _vp]),
     "eig_dot_diag_mv8": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "eig_gram_mv8": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "eig_orthonormalize_mv8": (_int, [_vp, _i64, _i64, _vp, _int]),
@@ -617,6 +618,11 @@ def stream_copy_GBs(ctx, n=1 << 27, reps=20, mode=None):
 
 def spmm_mv8(A, m, Qin, Qout):
     A.ctx.check(lib.eig_spmm_mv8(A.h, m, Qin.ptr, Qout.ptr))
+
+
+def spmm_blk_mv8(A, m, Qin, Qout):
+    """eig_spmm_blk_mv8: Qout = A Qin for square blocks 1..4 (A.n = nb_rows * br scalar rows)."""
+    A.ctx.check(lib.eig_spmm_blk_mv8(A.h, m, Qin.ptr, Qout.ptr))
 
 
 def dot_diag_mv8(ctx, n, m, Q1, Q2, dp):

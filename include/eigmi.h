@@ -332,8 +332,15 @@ int eig_stream_copy_timed(eig_ctx_t ctx, int64_t n, const double *x, double *y, 
                           double *avg_ms);
 
 /* ---------------------------------------------------------------- MultiVector<double,8> ---- */
-/* a2: Qout = A Qin, m columns (m % 8 == 0), br = bc = 1 (kernels_cpp.hh:626-657). */
+/* a2: Qout = A Qin, m columns (m % 8 == 0), br = bc = 1 (kernels_cpp.hh:626-657); blocks return
+ * EIG_ERR_BLOCKSIZE like the reference ("only implemented for FieldMatrix<..,1,1>"). */
 int eig_spmm_mv8(eig_mat_t mat, int64_t m, const double *Qin, double *Qout);
+/* The same product where the reference throws: square blocks br = bc = 1..4 on one rank (1x1: the
+ * kernels of eig_spmm_mv8).  Qin / Qout (distinct buffers) have n = nb_rows * br scalar rows (block
+ * row I, component r: row I br + r).  br > 1 runs the blocked kernel, bitwise the reference product
+ * on the matrix's scalar expansion (per row: stored blocks in order, c = 0..br-1 inside a block).
+ * Rectangular blocks: EIG_ERR_BLOCKSIZE. */
+int eig_spmm_blk_mv8(eig_mat_t mat, int64_t m, const double *Qin, double *Qout);
 /* a5: dp[j] = q1_j . q2_j, j < m (kernels_cpp.hh:24-55).  dp: device, m doubles. */
 int eig_dot_diag_mv8(eig_ctx_t ctx, int64_t n, int64_t m, const double *Q1, const double *Q2, double *dp);
 /* a6: G = Q1^T Q2 (m1 x m2, row-major, device) -- the tall-skinny panel product, on MFMA
@@ -401,7 +408,8 @@ int eig_fill_normal(eig_ctx_t ctx, int64_t count, unsigned seed, double *x);
 /* ---------------------------------------------------------------- drivers ------------------ */
 /* a12: StandardLargest (eigensolver.hh:28-112) on the device.  Mutates the matrix when
  * shift != 0 (like the reference).  eval_host[nev] (column order, unsorted, like the reference);
- * evec_host: nev vectors of n doubles each, or NULL.  *iters: the k at exit. */
+ * evec_host: nev vectors of n doubles each, or NULL.  *iters: the k at exit.
+ * 1x1 blocks only, like the reference (EIG_ERR_BLOCKSIZE otherwise). */
 int eig_standard_largest(eig_mat_t A, double shift, double tol, int maxiter, int nev, unsigned seed,
                          double *eval_host, double *evec_host, int *iters, int verbose);
 
@@ -527,7 +535,10 @@ int eig_inverse_mv8(eig_lu_t lu, int64_t m, double *Qin, double *Qout);
 /* StandardInverse (eigensolver.hh:116-198): inverse subspace iteration for the nev smallest
  * eigenvalues of A (+ shift; mutates A like the reference when shift != 0).  The LU of the shifted
  * A is computed on the host (eig_lu_create_bcsr) unless `lu` is given (factors of the SHIFTED A).
- * eval_host[nev] unsorted (column order), evec_host nev x n or NULL, *iters = k at exit. */
+ * eval_host[nev] unsorted (column order), evec_host nev x n or NULL, *iters = k at exit.
+ * Square blocks 1..4 on one rank, n = nb_rows * br: `lu` has n scalar rows (eig_lu_create_bcsr with
+ * the same br).  The reference throws on br > 1; eig_generalized_inverse below still does
+ * (EIG_ERR_BLOCKSIZE). */
 int eig_standard_inverse(eig_mat_t A, eig_lu_t lu, double shift, double tol, int maxiter, int nev, unsigned seed,
                          double *eval_host, double *evec_host, int *iters, int verbose);
 /* GeneralizedInverse (eigensolver.hh:204-351): A x = lambda B x by inverse subspace iteration with
@@ -545,7 +556,10 @@ int eig_generalized_inverse(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double shift,
  * ncv = 0: min(n, max(2 nev + 1, 20)); tol = 0: machine precision; maxit = 0: 100 nev restarts
  * (ARPACK++ defaults).  Converged when |beta_m y_m,i| <= tol |theta_i| for the nev wanted pairs.
  * eval_host[nev] ascending (the reference sorts the unshifted values, :636-648); evec_host nev x n
- * B-normalised, or NULL; *restarts: thick restarts taken. */
+ * B-normalised, or NULL; *restarts: thick restarts taken.
+ * Square blocks 1..4 on one rank, n = nb_rows * br, like the reference (which needs only mv and the
+ * factorisation, any FieldMatrix<double,r,c> at blockLevel 2): B NULL or with A's block size; sigma
+ * comes off the diagonal entries of the diagonal blocks (B NULL) or sigma B off the matching blocks. */
 int eig_shift_invert_solve(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma, int nev, int ncv, double tol,
                            int maxit, unsigned seed, double *eval_host, double *evec_host, int *restarts);
 /* The same with the Krylov method chosen.  EIG_SI_SINGLE: the one-vector thick-restart Lanczos
@@ -558,7 +572,9 @@ int eig_shift_invert_solve(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma, 
  * restarts.  EIG_SI_AUTO (0, what eig_shift_invert_solve and eig_shift_invert_adaptive use): the block
  * method when its basis (at most ~4 p + 1.5 nev columns) is at most n / 4 and its projection Gram
  * (basis x p, in 16 x 16 tiles) fits the 64 device reduction slots, else the one-vector one;
- * EIG_SI_BLOCK with an nev past that limit returns EIG_ERR_ARG. */
+ * EIG_SI_BLOCK with an nev past that limit returns EIG_ERR_ARG.  Blocked matrices (br > 1):
+ * EIG_SI_AUTO is the one-vector method, EIG_SI_BLOCK returns EIG_ERR_BLOCKSIZE (its panel kernels
+ * are FieldMatrix<..,1,1> code); eig_shift_invert_adaptive likewise runs the one-vector method. */
 #define EIG_SI_AUTO 0
 #define EIG_SI_SINGLE 1
 #define EIG_SI_BLOCK 2

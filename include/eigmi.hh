@@ -23,7 +23,11 @@
 //     dot_products_diagonal_blocked, dot_products_all_blocked, orthonormalize_blocked,
 //     B_orthonormalize_blocked, StandardLargest, StandardInverse, GeneralizedInverse) operating on host
 //     MultiVector<double,8>-compatible objects (anything with operator()(i,j), rows(), cols(),
-//     blocksize == 8), staged through HBM, plus DeviceMultiVector variants that stay resident;
+//     blocksize == 8), staged through HBM, plus DeviceMultiVector variants that stay resident.
+//     matmul_sparse_tallskinny_blocked and StandardLargest throw "only implemented for
+//     FieldMatrix<..,1,1>" on blocks like the reference's (the blocked product is the C entry
+//     eig_spmm_blk_mv8); StandardInverse and the symmetric shift-invert solves run square blocks 1..4
+//     on one rank (rows() = nb_rows * br); GeneralizedInverse and B_orthonormalize_blocked throw;
 //   * SHAPE / BLOCKSIZE statuses are thrown as std::invalid_argument (as the reference does,
 //     kernels_cpp.hh:29-32, :632-633, multivector.hh:48-49); other failures as std::runtime_error.
 #ifndef EIGMI_HH
@@ -245,6 +249,8 @@ class DeviceMultiVector {
 // --------------------------------------------- reference kernel names on host MultiVectors
 // Same signatures as kernels_cpp.hh; each call stages through HBM (one copy each way) -- the
 // drop-in form.  Loops that stay on the device use the DeviceMultiVector overloads.
+// A: FieldMatrix<double,1,1>; blocks throw std::invalid_argument as in the reference (the product
+// on FieldMatrix<double,b,b>, b = 2..4, is eig_spmm_blk_mv8 on device buffers of nb_rows * b rows).
 template <class MV>
 void matmul_sparse_tallskinny_blocked(MV &Qout, const Matrix &A, const MV &Qin)
 {

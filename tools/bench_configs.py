@@ -295,6 +295,27 @@ def c3(ctx):
     emit(config="C3 Q1 elasticity 64^3 3x3 BCSR", op="BCSR SpMV", us=round(ms * 1e3, 2), nnzb=nnzb,
          algorithmic_bytes=b, GBs=round(gbs, 1), frac=round(gbs / PEAK, 4), cpu_us=round(tc * 1e6, 1),
          cpu_GBs=round(b / tc / 1e9, 2))
+    # the blocked tall-skinny product (k_spmm_blk_mv8) beside it: back-to-back launches, one
+    # synchronisation (as C2's SpMM); the alternative a caller had before it is m eig_mv launches
+    n = 3 * nb
+    for m in (8, 32):
+        Q, Y = ctx.array(oracle.random_mv8(n, m, 1)), ctx.zeros(n * m)
+        eigmi.spmm_blk_mv8(M, m, Q, Y)
+        ctx.sync()
+
+        def spmm_batch(reps=20):
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                eigmi.spmm_blk_mv8(M, m, Q, Y)
+            ctx.sync()
+            return (time.perf_counter() - t0) / reps
+        tg = min(spmm_batch() for _ in range(3))
+        sb = 76 * nnzb + 4 * (nb + 1) + 2 * 8 * m * 3 * nb
+        emit(config="C3 Q1 elasticity 64^3 3x3 BCSR", op=f"blocked SpMM m={m}", kernel=M.kernel("spmm8"),
+             us=round(tg * 1e6, 2), algorithmic_bytes=sb, GBs=round(sb / tg / 1e9, 1),
+             frac=round(sb / tg / 1e9 / PEAK, 4), mv_us=round(ms * 1e3, 2), m_mv_us=round(m * ms * 1e3, 2),
+             ratio_vs_m_mv=round(tg / (m * ms * 1e-3), 4))
+        Q.free(), Y.free()
 
 
 def inv(ctx):
