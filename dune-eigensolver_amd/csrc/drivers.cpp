@@ -1390,7 +1390,7 @@ void lanczos_step(eig_mat_s &A, double *u, double *up, double *t, int j, Lanczos
   eig_ctx_t ctx = A.ctx;
   hipStream_t s = ctx->stream;
   const i64 own = A.own_offset;
-  const i64 n = A.nb_rows;
+  const i64 n = A.nb_rows * A.br;  // scalar rows
   auto mark = [&](int i) {
     if (ev && i < nev)
       EIG_HIP(hipEventRecordWithFlags(ev[i], s, ev_external ? hipEventRecordExternal : hipEventRecordDefault));
@@ -1511,9 +1511,13 @@ struct eig_lanczos_s {
 
 namespace {
 
+// The recurrence's matrices: 1x1 blocks, or square blocks 2..4 on one rank (k_lanczos_spmv_blk /
+// k_lanczos_fused_blk; the halo split of a distributed step is not built for block slices).
 void check_lanczos_matrix(const eig_mat_s *A)
 {
-  EIG_CHECK(A->br == 1 && A->bc == 1, EIG_ERR_BLOCKSIZE, "Lanczos driver: 1x1 blocks only");
+  EIG_CHECK(A->br == A->bc && A->br >= 1 && A->br <= 4, EIG_ERR_BLOCKSIZE,
+            "Lanczos recurrence: square blocks 1..4 only");
+  EIG_CHECK(lanczos_blocks_ok(*A), EIG_ERR_BLOCKSIZE, "Lanczos recurrence on blocks: one rank only");
   EIG_CHECK(A->nb_rows_global == A->nb_cols, EIG_ERR_SHAPE, "Lanczos needs a square matrix");
 }
 
@@ -1709,6 +1713,8 @@ extern "C" int eig_lanczos_create_ex(eig_mat_t A, int max_steps, const double *u
     EIG_CHECK(__builtin_popcount(flags & (EIG_LANCZOS_FUSED | EIG_LANCZOS_PIPELINED | EIG_LANCZOS_AUTO)) <= 1,
               EIG_ERR_ARG, "eig_lanczos_create_ex: FUSED, PIPELINED and AUTO are exclusive");
     check_lanczos_matrix(A);
+    EIG_CHECK(A->br == 1 || !(flags & EIG_LANCZOS_PIPELINED), EIG_ERR_BLOCKSIZE,
+              "eig_lanczos_create_ex: the pipelined step (an N > 1 form) is for 1x1 blocks");
     if (flags & EIG_LANCZOS_AUTO) flags = fused_step_pays(*A) ? EIG_LANCZOS_FUSED : 0;
     eig_ctx_t ctx = A->ctx;
     EIG_HIP(hipSetDevice(ctx->device));
@@ -1735,7 +1741,7 @@ extern "C" int eig_lanczos_create_ex(eig_mat_t A, int max_steps, const double *u
       double *U0 = ws->pipe ? ws->B[0]->d() : ws->fused ? ws->B[2]->d() : ws->B[0]->d();
       init_start(*A, U0, u0, seed);
       ws->lb = new LanczosBufs(max_steps, ws->max_launches);
-      launch_nrm2sq(A->nb_rows, U0 + A->own_offset, ws->lb->st.nsum, 0, s, ctx->red);
+      launch_nrm2sq(A->nb_rows * A->br, U0 + A->own_offset, ws->lb->st.nsum, 0, s, ctx->red);
       if (ws->fused)  // P0 = (u_0, 0) interleaved; the whole window (ghosts are refilled per step)
       {
         if (!ws->pipe)
@@ -1744,9 +1750,9 @@ extern "C" int eig_lanczos_create_ex(eig_mat_t A, int max_steps, const double *u
           EIG_HIP(hipMemcpy2DAsync(ws->B[0]->d(), 2 * sizeof(double), U0, sizeof(double), sizeof(double),
                                    A->window, hipMemcpyDeviceToDevice, s));
         }
-        // launch 0 takes step 0; the shift mu = trace / n from every rank's diagonal share
+        // launch 0 takes step 0; the shift mu = trace / n (n: scalar rows) from every rank's diagonal share
         EIG_HIP(hipMemsetAsync(ws->lb->st.ctl, 0, ws->lb->ictl.bytes(), s));
-        const double mu2[2] = {A->diag_sum, (double)A->nb_rows};
+        const double mu2[2] = {A->diag_sum, (double)(A->nb_rows * A->br)};
         EIG_HIP(hipMemcpyAsync(ws->lb->st.mu2, mu2, sizeof(mu2), hipMemcpyHostToDevice, s));
         allreduce_sum(ctx, ws->lb->st.mu2, 2, s);
       }

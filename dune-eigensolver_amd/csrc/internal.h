@@ -443,8 +443,16 @@ bool kuhn_pack_fits(const eig_mat_s &A);
 // pack where it fits, else the band arrays
 int kuhn_variant(const eig_mat_s &A);
 // Whether EIG_LANCZOS_AUTO takes the fused step on this image: every 1x1 image (round 3: without
-// register spills the fused step beats the two-kernel step on scattered images too).
+// register spills the fused step beats the two-kernel step on scattered images too); blocked
+// images: see the comment at its definition.
 bool fused_step_pays(const eig_mat_s &A);
+// Matrices the Lanczos step kernels take: 1x1 blocks, or square blocks 2..4 on one rank (the halo
+// split of a distributed step is over 1x1 slices only).
+inline bool lanczos_blocks_ok(const eig_mat_s &A)
+{
+  if (A.br == 1 && A.bc == 1) return true;
+  return A.br == A.bc && A.br >= 2 && A.br <= 4 && !A.ctx->distributed();
+}
 // Kernel family a whole-matrix launch of `op` (eig_mat_kernel_info's EIG_OP_*) picks on this image.
 std::string kernel_for(const eig_mat_s &A, int op);
 void launch_lanczos_spmv(const eig_mat_s &A, const double *u, const double *up, double *t, int j,

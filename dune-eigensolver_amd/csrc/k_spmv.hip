@@ -690,6 +690,112 @@ __global__ __launch_bounds__(kStreamThreads, min_waves<MODE>()) void k_lanczos_s
 }
 
 // ---------------------------------------------------------------------------------------------
+// The Lanczos step on square b x b blocks (blocked SELL-64 image, one rank: window = owned rows).
+// blk_rows_dot is k_spmv_blk's row loop: lane = block row, acc[r] of scalar row lane b + r starts
+// from 0.0 and takes the stored blocks in stored order, c = 0..b-1 inside a block, mul then add --
+// bitwise BCRSMatrix::mv on x (XPlain) or on u_k formed in the gather (XPair: the b pairs of a block
+// column are 16 b contiguous bytes, b 16-B loads).
+// ---------------------------------------------------------------------------------------------
+template <int B, class X>
+__device__ __forceinline__ void blk_rows_dot(const i64 *__restrict__ slice_ptr, const double *__restrict__ val,
+                                             const i32 *__restrict__ col, i64 s, int lane, const X &x,
+                                             double (&acc)[B])
+{
+  constexpr int BB = B * B;
+  const i64 base = slice_ptr[s];
+  const int width = (int)((slice_ptr[s + 1] - base) >> 6);
+#pragma unroll
+  for (int r = 0; r < B; ++r) acc[r] = 0.0;
+  for (int k = 0; k < width; ++k)
+  {
+    const i32 c = __builtin_nontemporal_load(col + base + (i64)k * 64 + lane);
+    if (c < 0) continue;
+    const double *vb = val + (base + (i64)k * 64) * BB + lane;
+    double a[BB];
+    typename X::raw xr[B];
+#pragma unroll
+    for (int t = 0; t < BB; ++t) a[t] = __builtin_nontemporal_load(vb + t * 64);
+#pragma unroll
+    for (int cc = 0; cc < B; ++cc) xr[cc] = x.load((i64)c * B + cc);
+    double xv[B];
+#pragma unroll
+    for (int cc = 0; cc < B; ++cc) xv[cc] = x.val(xr[cc]);
+#pragma unroll
+    for (int r = 0; r < B; ++r)
+    {
+      double sacc = acc[r];
+#pragma unroll
+      for (int cc = 0; cc < B; ++cc) sacc += a[r * B + cc] * xv[cc];
+      acc[r] = sacc;
+    }
+  }
+}
+
+// Waves / SIMD the blocked step kernels are built for: no scratch in any instantiation (the
+// resource-usage report).
+template <int B>
+constexpr int lanczos_blk_waves(bool fused)
+{
+  return B == 2 ? 8 : B == 3 ? (fused ? 6 : 8) : (fused ? 4 : 5);
+}
+
+// Kernel 1 on blocks: k_lanczos_spmv_b1's epilogue per scalar row.  Kernel 2 is k_lanczos_update on
+// the nbrows * b scalar rows.
+template <int B>
+__global__ __launch_bounds__(kStreamThreads, lanczos_blk_waves<B>(false)) void k_lanczos_spmv_blk(
+    i64 nbrows, const i64 *__restrict__ slice_ptr, const i32 *__restrict__ slices, i64 first, i64 count,
+    const double *__restrict__ val, const i32 *__restrict__ col, const double *__restrict__ u,
+    const double *__restrict__ up, double *__restrict__ t, int j, const double *__restrict__ nsum,
+    double *__restrict__ dot_out, double *__restrict__ beta_out, const double *__restrict__ carry, double *partials,
+    unsigned *ticket)
+{
+  __shared__ double tot[1];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const double beta = sqrt(nsum[j]);
+  const double sig = 1.0 / beta;
+  const double gam = (j > 0) ? beta * (1.0 / sqrt(nsum[j - 1])) : 0.0;
+  i64 b, e;
+  chunk_of(count, b, e);
+  double d = 0.0;
+  for (i64 it = b + wave; it < e; it += kWaves)
+  {
+    const i64 s = slices ? (i64)slices[first + it] : first + it;
+    const i64 row = s * 64 + lane;
+    const bool ok = row < nbrows;
+    // epilogue operands issued before the row loop so their latency hides under the matrix stream
+    double upv[B], uv[B];
+#pragma unroll
+    for (int r = 0; r < B; ++r)
+    {
+      upv[r] = (ok && j > 0) ? up[row * B + r] : 0.0;
+      uv[r] = ok ? u[row * B + r] : 0.0;
+    }
+    double acc[B];
+    blk_rows_dot<B>(slice_ptr, val, col, s, lane, XPlain{u}, acc);
+    if (ok)
+    {
+#pragma unroll
+      for (int r = 0; r < B; ++r)
+      {
+        double ti = acc[r] * sig;
+        if (j > 0) ti = ti - gam * upv[r];
+        t[row * B + r] = ti;
+        d += ti * uv[r];
+      }
+    }
+  }
+  double v[1] = {d};
+  if (grid_sum<1, kStreamThreads>(v, partials, ticket, tot))
+  {
+    if (threadIdx.x == 0)
+    {
+      dot_out[0] = carry ? (carry[0] + tot[0]) : tot[0];
+      if (beta_out) beta_out[0] = beta;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Fused one-reduction Lanczos step.  u_k = t_{k-1} - c u_{k-1} is formed inside the
 // gathers of the SpMV that needs it (XPair), and its squared norm is PREDICTED from the previous
 // step's reductions instead of being reduced before the SpMV:
@@ -1081,6 +1187,68 @@ __global__ __launch_bounds__(kStreamThreads, CPF ? 5 : fused_b1_waves<MODE>()) v
         double ti = (acc[q] - mu * uk) * sig;
         if (k > 0) ti = ti - gam * uv[q];
         Pout[own + r] = dpair{ti, uk};
+        d += ti * uk;
+        q2 += ti * ti;
+        m2 += uk * uk;
+      }
+    }
+  }
+  double v[3] = {d, q2, m2};
+  fused_finish<2>(v, partials, ticket, tot, out, carry, fa);
+}
+
+// The guarded fused step on square b x b blocks: k_lanczos_fused_b1's control words, branches and
+// per-row epilogue over the nbrows * b scalar rows (one rank: pairs indexed by the scalar row), the
+// row products by blk_rows_dot on the pairs.
+template <int B>
+__global__ __launch_bounds__(kStreamThreads, lanczos_blk_waves<B>(true)) void k_lanczos_fused_blk(
+    i64 nbrows, const i64 *__restrict__ slice_ptr, const i32 *__restrict__ slices, i64 first, i64 count,
+    const double *__restrict__ val, const i32 *__restrict__ col, const dpair *__restrict__ P,
+    dpair *__restrict__ Pout, FusedArgs fa, double *__restrict__ out, const double *__restrict__ carry,
+    double *partials, unsigned *ticket)
+{
+  __shared__ double tot[3];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const FusedStep fs = fused_begin(fa);
+  if (fs.act == kFusedHalt || fs.act == kFusedNoop)
+  {
+    double z[3] = {0.0, 0.0, 0.0};
+    if (fa.xch & kXchPublish) fused_finish<2>(z, partials, ticket, tot, out, nullptr, fa);
+    else fused_idle(out);
+    return;
+  }
+  const double c = fs.c, gam = fs.gam, sig = fs.sig, mu = fs.mu;
+  const int k = fs.j;
+  if (fs.act == kFusedRepair)
+  {
+    double v[3] = {0.0, 0.0, fused_repair_rows(0, nbrows * B, 0, c, P, Pout)};
+    fused_finish<2>(v, partials, ticket, tot, out, carry, fa);
+    return;
+  }
+  const XPair xc{P, c};
+  double d = 0.0, q2 = 0.0, m2 = 0.0;
+  i64 b, e;
+  chunk_of(count, b, e);
+  for (i64 it = b + wave; it < e; it += kWaves)
+  {
+    const i64 s = slices ? (i64)slices[first + it] : first + it;
+    const i64 row = s * 64 + lane;
+    const bool ok = row < nbrows;
+    // the rows' own pairs issued before the row loop so their latency hides under the matrix stream
+    dpair pv[B];
+#pragma unroll
+    for (int r = 0; r < B; ++r) pv[r] = ok ? P[row * B + r] : dpair{0.0, 0.0};
+    double acc[B];
+    blk_rows_dot<B>(slice_ptr, val, col, s, lane, xc, acc);
+    if (ok)
+    {
+#pragma unroll
+      for (int r = 0; r < B; ++r)
+      {
+        const double uk = pv[r].x - c * pv[r].y;
+        double ti = (acc[r] - mu * uk) * sig;
+        if (k > 0) ti = ti - gam * pv[r].y;
+        Pout[row * B + r] = dpair{ti, uk};
         d += ti * uk;
         q2 += ti * ti;
         m2 += uk * uk;
@@ -3022,7 +3190,18 @@ void launch_lanczos_spmv(const eig_mat_s &A, const double *u, const double *up, 
                          const LanczosState &st, const i32 *slices, i64 first, i64 count, double *dot_out,
                          double *beta_out, const double *carry, int ticket, hipStream_t s, ReduceWS red)
 {
-  EIG_CHECK(A.br == 1 && A.bc == 1, EIG_ERR_BLOCKSIZE, "Lanczos driver: 1x1 blocks only");
+  EIG_CHECK(lanczos_blocks_ok(A), EIG_ERR_BLOCKSIZE, "Lanczos step: square blocks 1..4 only (blocks: one rank)");
+#define EIG_LZB(B_)                                                                                          \
+  if (A.br == B_)                                                                                            \
+  {                                                                                                          \
+    hipLaunchKernelGGL((k_lanczos_spmv_blk<B_>),                                                             \
+                       dim3(grid_for_slices(k_lanczos_spmv_blk<B_>, count, A.ctx->num_cu)), dim3(kStreamThreads), \
+                       0, s, A.nb_rows, A.slice_ptr, slices, first, count, A.val, A.col, u, up, t, j, st.nsum, \
+                       dot_out, beta_out, carry, red.partials, red.ticket(ticket));                          \
+    return;                                                                                                  \
+  }
+  EIG_LZB(2) EIG_LZB(3) EIG_LZB(4)
+#undef EIG_LZB
   if (!carry)
   {
     const int mode = image_mode(A);
@@ -3062,7 +3241,7 @@ void launch_lanczos_fused(const eig_mat_s &A, const double *P, double *Pout, con
                           const i32 *slices, i64 first, i64 count, const double *carry, double *out, int ticket,
                           hipStream_t s, ReduceWS red)
 {
-  EIG_CHECK(A.br == 1 && A.bc == 1, EIG_ERR_BLOCKSIZE, "Lanczos driver: 1x1 blocks only");
+  EIG_CHECK(lanczos_blocks_ok(A), EIG_ERR_BLOCKSIZE, "Lanczos step: square blocks 1..4 only (blocks: one rank)");
   FusedArgs fa{fl.st.nsum, fl.st.alpha, fl.st.beta, fl.st.fred, fl.st.ctl, fl.st.aux, fl.st.mu2, fl.st.pn, fl.L,
                fl.force, 0, Mailbox{}};
   if (fl.xch)
@@ -3071,6 +3250,18 @@ void launch_lanczos_fused(const eig_mat_s &A, const double *P, double *Pout, con
     fa.xch = fl.xch & kXchPublish;
     fa.mb = A.ctx->mbox->dev;
   }
+#define EIG_LFB(B_)                                                                                          \
+  if (A.br == B_)                                                                                            \
+  {                                                                                                          \
+    hipLaunchKernelGGL((k_lanczos_fused_blk<B_>),                                                            \
+                       dim3(grid_for_slices(k_lanczos_fused_blk<B_>, count, A.ctx->num_cu)),                 \
+                       dim3(kStreamThreads), 0, s, A.nb_rows, A.slice_ptr, slices, first, count, A.val, A.col, \
+                       reinterpret_cast<const dpair *>(P), reinterpret_cast<dpair *>(Pout), fa, out, carry,   \
+                       red.partials, red.ticket(ticket));                                                    \
+    return;                                                                                                  \
+  }
+  EIG_LFB(2) EIG_LFB(3) EIG_LFB(4)
+#undef EIG_LFB
   if (!carry)
   {
     const int mode = image_mode(A);
@@ -3269,7 +3460,14 @@ bool launch_spmm_march_dot_gram(const eig_mat_s &A, i64 m, const double *X, doub
 
 void lanczos_kernel_info(const eig_mat_s &A, bool fused, std::string &name, i64 &bytes)
 {
-  const i64 n = A.nb_rows, vec = fused ? 32 * n : 24 * n;  // fused: (t, u) pairs in + out; K1: x, u_{j-1}, t
+  const i64 n = A.nb_rows * A.br, vec = fused ? 32 * n : 24 * n;  // fused: (t, u) pairs in + out; K1: x, u_{j-1}, t
+  if (A.br == A.bc && A.br >= 2 && A.br <= 4)
+  {
+    // blocked SELL-64 image: every padded block value and column index, the slice pointers, the vectors
+    bytes = (8 * (i64)A.br * A.bc + 4) * A.nnzb_padded + 8 * (A.nslices + 1) + vec;
+    name = fused ? "k_lanczos_fused_blk" : "k_lanczos_spmv_blk";
+    return;
+  }
   const int mode = A.br == 1 && A.bc == 1 ? image_mode(A) : kExplicit;
   if (is_sym_mode(mode))
   {
@@ -3311,6 +3509,11 @@ i64 sell_image_bytes(const eig_mat_s &A)
 // scrambled + RCM 256^3 Poisson, the spill write-back being the 3.5x write excess PMC showed; at 6
 // waves / SIMD without the spills it runs 408 us, step 415 vs 436 us, PMC 0.97x of the CSR bytes:
 // profiles/r03ah_csr*.)
+// Blocked images (square blocks 2..4) keep the two-kernel step: at C3 (Q1 elasticity 64^3, 3x3
+// blocks, 521 MB of matrix against 25 MB of vectors) the two-kernel step took 99.46 / 99.33 us and
+// the fused step 103.69 / 103.49 us, alternated in one process (profiles/blocked_lanczos_c3.jsonl) --
+// kernel trace: k_lanczos_fused_blk 105.9 us against k_lanczos_spmv_blk 91.7 + k_lanczos_update
+// 8.5 us; the 16-B gathers cost more than the update kernel they save.
 bool fused_step_pays(const eig_mat_s &A) { return A.br == 1 && A.bc == 1; }
 
 std::string kernel_for(const eig_mat_s &A, int op)

@@ -686,7 +686,8 @@ def standard_largest(A, shift, tol, maxiter, nev, seed=123, want_evec=True, verb
 
 
 def _lflags(fused, pipelined):
-    """fused: True / False / "auto" (EIG_LANCZOS_AUTO: fused on every 1x1 image)."""
+    """fused: True / False / "auto" (EIG_LANCZOS_AUTO: fused on every 1x1 image, the two-kernel step
+    on blocked images)."""
     if pipelined:
         return LANCZOS_PIPELINED
     return LANCZOS_AUTO if fused == "auto" else LANCZOS_FUSED if fused else 0
@@ -694,7 +695,9 @@ def _lflags(fused, pipelined):
 
 def lanczos_run(A, steps, u0=None, seed=123, timed=False, fused=False, pipelined=False):
     """fused: the one-reduction single-kernel step (EIG_LANCZOS_FUSED) instead of K1 + K2;
-    pipelined: the one-reduction step with the SpMV on t_{k-1} (EIG_LANCZOS_PIPELINED)."""
+    pipelined: the one-reduction step with the SpMV on t_{k-1} (EIG_LANCZOS_PIPELINED).
+    A: square blocks 1..4 on one rank (n = nb_rows * br scalar rows; rectangular or distributed
+    blocked matrices and pipelined on blocks raise EigShapeError, EIG_ERR_BLOCKSIZE)."""
     alpha = np.zeros(max(steps, 1))
     beta = np.zeros(steps + 1)
     t = Timing()
@@ -706,7 +709,9 @@ def lanczos_run(A, steps, u0=None, seed=123, timed=False, fused=False, pipelined
 
 class LanczosWorkspace:
     """eig_lanczos_t: the three-term recurrence as a persistent workspace (setup outside any
-    timed region; step() advances and returns the eig_timing of that batch)."""
+    timed region; step() advances and returns the eig_timing of that batch).  A: square blocks 1..4
+    on one rank (blocks: k_lanczos_spmv_blk / k_lanczos_fused_blk; fused="auto" takes the two-kernel
+    step there; pipelined is 1x1 only, EIG_ERR_BLOCKSIZE otherwise)."""
 
     def __init__(self, A, max_steps, u0=None, seed=123, fused=False, pipelined=False):
         self.A = A

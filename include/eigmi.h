@@ -416,7 +416,11 @@ int eig_standard_largest(eig_mat_t A, double shift, double tol, int maxiter, int
 /* Lanczos three-term recurrence on A (the loop ARPACK's dsaupd runs around multMv):
  * `steps` steps from the start vector u0 (device, window layout; NULL = mt19937(seed) normal).
  * Only three vectors are kept (no basis); alpha_host[steps], beta_host[steps+1] receive the
- * tridiagonal T (beta[0] = ||u0||).  This is the benchmark's unit of work. */
+ * tridiagonal T (beta[0] = ||u0||).  This is the benchmark's unit of work.
+ * Matrices (eig_lanczos_run and the workspace API below): square blocks br = bc = 1..4 on one rank,
+ * vectors of n = nb_rows * br scalar rows (blocks: k_lanczos_spmv_blk / k_lanczos_fused_blk, the
+ * arithmetic of the 1x1 steps on the matrix's scalar expansion); rectangular blocks, distributed
+ * blocked matrices and EIG_LANCZOS_PIPELINED on blocks return EIG_ERR_BLOCKSIZE. */
 typedef struct eig_timing {
   double total_ms;        /* wall time of the stepping loop (device events, first to last) */
   double spmv_ms;         /* summed duration of the fused SpMV kernel launches */
@@ -434,19 +438,22 @@ enum eig_lanczos_flags {
    * mu = trace(A)/n (alpha reported unshifted), and a launch whose prediction keeps less than 1e-2
    * of ||t||^2 repairs instead (forms u_k, reduces its exact norm; the next launch takes the step),
    * decided on the device.  beta[k] of eig_lanczos_tridiag is always the exact ||u_k||.  Same
-   * Krylov process as the two-kernel step; alpha/beta agree with it to its own rounding spread. */
+   * Krylov process as the two-kernel step; alpha/beta agree with it to its own rounding spread.
+   * Square blocks 1..4 on one rank (mu = trace / n over the n = nb_rows * br scalar rows). */
   EIG_LANCZOS_FUSED = 4,
   /* Pipelined one-reduction step, for N > 1 ranks: the same scalars, guard and
    * repairs as EIG_LANCZOS_FUSED, but a step's SpMV multiplies t_{k-1} (S = A t_{k-1}, an eig_mv
    * launch that needs no scalar of the previous step) and a row kernel forms u_k = t_{k-1} - c u_{k-1},
    * z_k = S - c z_{k-1} (= A u_k) and t_k; so the previous step's 3-value allreduce (second RCCL
    * communicator, its own stream) overlaps the SpMV and the halo of t (8 B per row, not 16).
-   * Costs 56 B per row more than the fused step on one GPU.  Exclusive with EIG_LANCZOS_FUSED. */
+   * Costs 56 B per row more than the fused step on one GPU.  Exclusive with EIG_LANCZOS_FUSED.
+   * 1x1 blocks only (EIG_ERR_BLOCKSIZE on blocks). */
   EIG_LANCZOS_PIPELINED = 8,
   /* Pick per matrix at creation: EIG_LANCZOS_FUSED for every 1x1 (scalar) matrix image -- band,
    * stencil or scattered (256^3 scrambled + RCM: 415 us per fused step vs 436 for the two-kernel
-   * step) -- the two-kernel step for blocked images.  eig_lanczos_ws_info reports the
-   * choice. */
+   * step) -- the two-kernel step for blocked images (square blocks 2..4: measured at
+   * Q1 elasticity 64^3, 3x3 blocks, 99.4 us per two-kernel step vs 103.6 us per fused step, DESIGN.md
+   * 5b).  eig_lanczos_ws_info reports the choice. */
   EIG_LANCZOS_AUTO = 16
 };
 int eig_lanczos_run(eig_mat_t A, int steps, const double *u0, unsigned seed, int flags,
@@ -484,7 +491,8 @@ int eig_lanczos_replay(eig_lanczos_t ws, eig_timing *timing);
  * twice, the DGKS scheme ARPACK uses) and Ritz extraction from T.  which: EIG_WHICH_LA (largest
  * algebraic) or EIG_WHICH_SA (smallest algebraic).  eval_host[nev] sorted (LA: descending,
  * SA: ascending); evec_host: nev owned-row vectors or NULL; resid_host[nev] (optional):
- * ||A y - theta y|| of each returned pair (computed on the device). */
+ * ||A y - theta y|| of each returned pair (computed on the device).
+ * 1x1 blocks only (EIG_ERR_BLOCKSIZE otherwise), unlike the recurrence above. */
 enum eig_which { EIG_WHICH_LA = 0, EIG_WHICH_SA = 1 };
 int eig_lanczos_solve(eig_mat_t A, int nev, int ncv, int which, unsigned seed, double *eval_host,
                       double *evec_host, double *resid_host);

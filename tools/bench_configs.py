@@ -5,7 +5,8 @@
       oracle (reference CPU path) timed on the same inputs
   C2  3-D Poisson 128^3: SpMV (cache-resident: 217 MB < 256 MB MALL), Lanczos step, the b = 8
       SpMM, block Gram-Schmidt (m = 8, 32) and one StandardLargest iteration vs the CPU path
-  C3  3-D Q1 elasticity 64^3, 3x3 blocks: BCSR SpMV against 76 nnzb + 4 (nb+1) + 48 nb bytes
+  C3  3-D Q1 elasticity 64^3, 3x3 blocks: BCSR SpMV against 76 nnzb + 4 (nb+1) + 48 nb bytes, the
+      blocked SpMM, and the Lanczos step on blocks (two-kernel and fused, alternated twice)
   INV inverse iteration with exported LU factors on the harness matrices:
       matmul_inverse_tallskinny_blocked (m = 8), StandardInverse, GeneralizedInverse (GenEO pencil)
       and computeGenSymShiftInvertMinMagnitude, GPU vs the oracle / scipy ARPACK on the host
@@ -316,6 +317,27 @@ def c3(ctx):
              frac=round(sb / tg / 1e9 / PEAK, 4), mv_us=round(ms * 1e3, 2), m_mv_us=round(m * ms * 1e3, 2),
              ratio_vs_m_mv=round(tg / (m * ms * 1e-3), 4))
         Q.free(), Y.free()
+    # the Lanczos step on the blocked image: the two-kernel step (k_lanczos_spmv_blk + k_lanczos_update)
+    # and the fused one-reduction step (k_lanczos_fused_blk), alternated twice so the run-to-run
+    # spread shows; per variant 10 warm-up steps, 200 steps untimed inside (step_us, from the batch's
+    # two events) and 200 with per-kernel events (kernel_us); eig_mv timed again beside each
+    steps = 200
+    for rnd in range(2):
+        for fused in (False, True):
+            mv_ms = M.mv_timed(x, y, 100)
+            ws = eigmi.LanczosWorkspace(M, 10 + 2 * steps, seed=123, fused=fused)
+            ws.step(10)
+            t = ws.step(steps)
+            tk = ws.step(steps, timed=True if fused else "detail")
+            launches = int(tk.spmv_launches)
+            kus = tk.spmv_ms / launches * 1e3
+            extra = {} if fused else {"k2_us": round(tk.update_ms / steps * 1e3, 2)}
+            emit(config="C3 Q1 elasticity 64^3 3x3 BCSR", op="Lanczos step (fused)" if fused else "Lanczos step (classic: K1 + update)",
+                 round=rnd, variant=ws.variant, step_us=round(t.total_ms / steps * 1e3, 2), kernel=ws.kernel,
+                 kernel_us=round(kus, 2), kernel_launches=launches, model_bytes=ws.kernel_bytes,
+                 kernel_frac=round(ws.kernel_bytes / (kus * 1e-6) / 1e9 / PEAK, 4), mv_us=round(mv_ms * 1e3, 2),
+                 step_vs_mv=round(t.total_ms / steps / mv_ms, 4), kernel_vs_mv=round(kus * 1e-3 / mv_ms, 4), **extra)
+            ws.close()
 
 
 def inv(ctx):
