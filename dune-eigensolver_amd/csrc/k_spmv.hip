@@ -1301,11 +1301,16 @@ struct MarchPlan {
   const double *pack;
   // eig_mat_tune(EIG_TUNE_CACHE) bits for the value march (measurement): 2 = the value streams with the
   // default cache policy instead of nontemporal, 4 = the +D pair stream nontemporal
+  // 8 = every launch marches upward, 16 = every launch of variants 22 / 23 marches downward (MarchPlan::down)
   int cache;
   // geo2 value marches: 4 = a workgroup's 4 waves march the same 64 x of 4 consecutive y lines (their
   // +-nx gathers then mostly read lines their sibling waves just loaded on the same CU) instead of the
   // 4 x runs of one line; 0 = the item order (eig_mat_tune EIG_TUNE_MARCH_LINES)
   int lines;
+  // the 2-line value marches 22 / 23: 1 = every plane run is marched from its last plane down to its first
+  // (march_rows_geo2_2l<DOWN>); wave-uniform, a kernel argument -- a launch captured into a graph replays
+  // its own direction
+  int down;
 };
 // store helper of the geo2 epilogues: temporal when the plan says the vectors fit the MALL
 template <class T>
@@ -1667,8 +1672,29 @@ __device__ __forceinline__ void march_rows_geo2(const SellB1 &A, const MarchPlan
 // per column on wide planes (march_plan, round 6) 4 M rows 45.6 vs 46.0 us, 2 M rows 27.6 either way --
 // the threshold is 4 M.
 constexpr bool kMarch2lDefault = true;
+// DOWN (variants 22 / 23, MarchPlan::down; DESIGN section 4e "serpentine"): the same work items march their
+// runs from plane z1 - 1 down to z0, so a launch that follows an upward one starts on the planes that one
+// touched last -- what the 256 MiB memory-side cache can still hold of the previous launch's pair stores
+// and of the value pack.  What is carried and what is loaded swap: the centres, the plane's diagonal
+// values and its two +D products a(w, w + D) u(w + D), already rounded (both factors were at hand one
+// plane above: the (+D, 0) pair loaded there and that plane's centre), ride in registers; per plane the -D
+// operands (the next centres) and the (+D, 0) pairs of the plane BELOW are loaded -- their .x is this
+// plane's mirrored -D value, and .x times this plane's centre and .y are what the next plane carries.
+// Each row still adds its seven products in the order -D, -nx, -1, 0, +1, +nx, +D; without contraction
+// (-ffp-contract=off) a product rounds the same wherever it is formed, so the rows are bitwise the upward
+// ones; a lane adds its rows into the launch's three sums top plane first.
+// A fused launch of variant 22 / 23 marches down when its launch index is odd (launch_lanczos_fused).
+// Measured at 256^3, one process, 7 interleaved rounds (profiles/r07_serpentine_ab.jsonl): every
+// launch upward 191.8 us (max - min over rounds 1.0), every launch downward 198.4 us (the downward body is
+// the slower one), alternating 185.0 us -- each launch gains what the memory-side cache still holds of the
+// one before it.  Plain pair stores or default-policy (+D, 0) loads (EIG_TUNE_CACHE 1 / 2) change nothing
+// there (184.8 - 185.0 us), so the nontemporal defaults stay.
+constexpr bool kMarch2lSerpentine = true;
+constexpr bool march_down_variant(int uni) { return uni == 22 || uni == 23; }  // (24 spills marching upward alone)
+template <int UNI>
+constexpr bool kMarchDownBody = march_down_variant(UNI);
 
-template <class X, class EPI, class PRE>
+template <bool DOWN, class X, class EPI, class PRE>
 __device__ __forceinline__ void march_rows_geo2_2l(const SellB1 &A, const MarchPlan &mp, i64 own, int lane, int wave,
                                                    X x, EPI &epi, PRE &pre)
 {
@@ -1696,6 +1722,89 @@ __device__ __forceinline__ void march_rows_geo2_2l(const SellB1 &A, const MarchP
   const SymImg &S = A.sym;
   const dpair *P01 = reinterpret_cast<const dpair *>(mp.pack), *P23 = P01 + S.ld;
   const bool le = lane == 0 && x0 > 0;  // lane 0's mirrored -1 value (row x0 - 1) exists
+  if constexpr (DOWN)
+  {
+    // one row's sum: the seven products in ascending-offset order; the +D product comes in already rounded
+    // (carried from the plane above, where both its factors were at hand: two registers per row less than
+    // carrying the factors, which is what keeps every load of a plane in flight at 5 waves per SIMD)
+    auto row = [&](double amD, double vmD, double an, double vn, double am, double vl, double a0, double vc, double a1,
+                   double vr, double aq, double vq, double prodD) {
+      double acc = 0.0;
+      acc += amD * vmD;
+      acc += an * vn;
+      acc += am * vl;
+      acc += a0 * vc;
+      acc += a1 * vr;
+      acc += aq * vq;
+      acc += prodD;
+      return acc;
+    };
+    w += (z1 - 1 - z0) * D;
+    vo = (unsigned)w * SZ;
+    const bool above = z1 + mp.gz0 < mp.gz;  // plane z1 exists globally: the top plane's +D operands
+    raw pu0{}, pu1{};
+    if (above)
+    {
+      bload(rs, vo + Db, pu0);
+      bload(rs, vo + nxb + Db, pu1);
+    }
+    const dpair p0a = (mp.cache & 2) ? P01[w] : __builtin_nontemporal_load(P01 + w);
+    const dpair p1a = (mp.cache & 2) ? P01[w + gx] : __builtin_nontemporal_load(P01 + w + gx);
+    raw c0, c1;
+    bload(rs, vo, c0);
+    bload(rs, vo + nxb, c1);
+    if (!pre(x)) return;
+    // carried: the plane's diagonal values and its +D products a(w, w + D) u(w + D)
+    double a00 = p0a.y, a01 = p1a.y;
+    double pD0 = p0a.x * (above ? x.val(pu0) : 0.0), pD1 = p1a.x * (above ? x.val(pu1) : 0.0);
+    // one plane; BELOW: the plane below exists globally (global plane 0 is peeled off the loop, so the loop
+    // body has no branch that depends on the plane: there the -D operands come through the zero-record
+    // descriptor and the (+D, 0) pairs of the plane below are exact zeros, not loaded)
+    auto plane = [&](auto below_c) {
+      constexpr bool below = decltype(below_c)::value;
+      // the HBM streams first (the -D operands open each row's sum), ahead of the branches of the masked
+      // edge loads: issued after them the compiler placed them behind a full wait, two round trips per plane
+      raw eg0, eg1, xn0, xq1, m0, m1;
+      bload(below ? rs : r0, vo - Db, m0);
+      bload(below ? rs : r0, vo + nxb - Db, m1);
+      dpair q0a = dpair{0.0, 0.0}, q1a = dpair{0.0, 0.0};
+      if constexpr (below)
+      {
+        q0a = (mp.cache & 2) ? P01[w - D] : __builtin_nontemporal_load(P01 + w - D);
+        q1a = (mp.cache & 2) ? P01[w + gx - D] : __builtin_nontemporal_load(P01 + w + gx - D);
+      }
+      const dpair p0b = P23[w], p1b = P23[w + gx];
+      bload(rs, vo + eoff, eg0);
+      bload(rs, vo + nxb + eoff, eg1);
+      bload(rn, vo + dnb, xn0);
+      bload(rq, vo + nxb + dqb, xq1);
+      const double an0 = has_n ? P23[w + mp.dn].y : 0.0;
+      const double ae0 = le ? P23[w - 1].x : 0.0, ae1 = le ? P23[w + gx - 1].x : 0.0;
+      const double vc0 = x.val(c0), vc1 = x.val(c1);
+      const double ve0 = x.val(eg0), ve1 = x.val(eg1);
+      const double acc0 = row(q0a.x, x.val(m0), an0, x.val(xn0), lane_shift_or<false>(p0b.x, ae0),
+                              lane_shift_or<false>(vc0, ve0), a00, vc0, p0b.x, lane_shift_or<true>(vc0, ve0), p0b.y,
+                              vc1, pD0);
+      const double acc1 = row(q1a.x, x.val(m1), p0b.y, vc0, lane_shift_or<false>(p1b.x, ae1),
+                              lane_shift_or<false>(vc1, ve1), a01, vc1, p1b.x, lane_shift_or<true>(vc1, ve1), p1b.y,
+                              x.val(xq1), pD1);
+      epi(w - own32, w, acc0, c0);
+      epi(w + gx - own32, w + gx, acc1, c1);
+      // the plane below: its +D entry times this plane's operand, its diagonal, its centres
+      pD0 = q0a.x * vc0;
+      pD1 = q1a.x * vc1;
+      a00 = q0a.y;
+      a01 = q1a.y;
+      c0 = m0;
+      c1 = m1;
+      w -= D;
+      vo -= Db;
+    };
+    const bool floor0 = zg0 == 0;  // the run ends on global plane 0
+    for (int z = z1 - 1; z >= z0 + (floor0 ? 1 : 0); --z) plane(std::true_type{});
+    if (floor0) plane(std::false_type{});
+    return;
+  }
   double amD0 = 0.0, amD1 = 0.0;
   raw pm0{}, pm1{};
   if (zg0 > 0)
@@ -2049,7 +2158,13 @@ __device__ __forceinline__ void march_rows(const SellB1 &A, const MarchPlan &mp,
   }
   else if constexpr (kTraits<UNI>.family == kMarchGeo2L2)
   {
-    march_rows_geo2_2l(A, mp, own, lane, wave, x, epi, pre);
+    if constexpr (kMarchDownBody<UNI>)
+      if (mp.down)
+      {
+        march_rows_geo2_2l<true>(A, mp, own, lane, wave, x, epi, pre);
+        return;
+      }
+    march_rows_geo2_2l<false>(A, mp, own, lane, wave, x, epi, pre);
     return;
   }
   else if constexpr (kTraits<UNI>.family == kMarchGeo2)
@@ -3064,6 +3179,9 @@ static MarchPlan march_plan(const eig_mat_s &A, int mode, i64 zb = 0, i64 ze = -
   // 8.0 us)
   mp.tstore = fused && T.geo2_path() && (vectors_fit_mall(A) || (A.tune_cache & 1));
   mp.cache = A.tune_cache;
+  // EIG_TUNE_CACHE 16: every launch of the 2-line variants with a downward body marches down (eig_mv and the
+  // classic K1 too, when tuned onto them).  The fused step's alternation (neither bit, or both): launch_lanczos_fused
+  mp.down = march_down_variant(uni) && (A.tune_cache & 24) == 16;
   // line groups (MarchTraits::line_groups, on grids of whole 64-x runs and 4-line groups)
   mp.lines = A.tune_march_lines == 4 && T.line_groups && mp.gx % 64 == 0 &&
                      mp.gx > 0 && mp.gy % 4 == 0 && (i64)mp.gx * mp.gy == D
@@ -3265,9 +3383,15 @@ void launch_lanczos_fused(const eig_mat_s &A, const double *P, double *Pout, con
   if (!carry)
   {
     const int mode = image_mode(A);
-    const MarchPlan mp = launch_plan(A, mode, slices, first, count, true);
+    MarchPlan mp = launch_plan(A, mode, slices, first, count, true);
     if (mp.nseg > 0)
     {
+      // serpentine: odd launches march down, so each launch starts on the planes the one before it
+      // finished on (whole-matrix and interior-plane launches alike; a repair launch marches nothing
+      // but takes an index, so the parity simply continues).  EIG_TUNE_CACHE 8 / 16 fix the direction,
+      // 24 alternates whatever the default is
+      if (march_down_variant(mp.uni) && ((A.tune_cache & 24) == 24 || (kMarch2lSerpentine && !(A.tune_cache & 24))))
+        mp.down = fl.L & 1;
       march_launch(MarchDispatch{}, A, mode, mp.uni, [&](auto mt, auto span1, auto uni) {
         hipLaunchKernelGGL((k_lanczos_fused_march<decltype(mt), span1(), uni()>), dim3(march_grid(mp)),
                            dim3(kStreamThreads), 0, s, A.nb_rows, A.own_offset, sell_b1(A), mp,

@@ -272,7 +272,14 @@ enum { EIG_TUNE_MARCH_RUNS = 1, EIG_TUNE_BOX_SEGS = 2, EIG_TUNE_MARCH_PREFETCH =
  * 0 = automatic.  Results bitwise identical. */
 /* EIG_TUNE_CACHE (measurement; fused value march): bit 0 = the (t, u) pairs stored with plain (MALL-
  * allocating) stores instead of nontemporal ones, bit 1 = the value streams with the default cache
- * policy, bit 2 = the +D pair stream nontemporal.  Results unchanged. */
+ * policy, bit 2 = the +D pair stream nontemporal.  Results unchanged.
+ * Direction of the 2-line value marches (variants 22 / 23; every row's sum stays bitwise, a launch's
+ * three sums add their rows in another order): bit 3 (8) = every launch marches its plane runs upward;
+ * bit 4 (16) = every launch through variants 22 / 23 marches them downward, from each run's last plane
+ * to its first -- eig_mv and the classic step too where EIG_TUNE_MARCH_PREFETCH 16 / 17 routes them
+ * there (tests and A/B only); both bits (24) = fused launches alternate, downward when the launch
+ * index is odd, whatever the built-in default is.  Neither bit: the default (kMarch2lSerpentine in
+ * k_spmv.hip). */
 /* EIG_TUNE_HALO (distributed Lanczos steps): 0 = the interior planes run while the halo is in flight
  * and the boundary planes after it (two launches, the default); 1 = the exchange first, then ONE
  * launch over all owned rows (no second launch's fixed cost; the exchange is exposed).  The step's

@@ -143,6 +143,8 @@ def main():
                           "kernel": M.kernel({"mv": "spmv", "fused": "fused", "pipelined": "spmv",
                                                              "classic": "k1"}[op]),
                           "kernel_us_med": round(km, 2), "kernel_us_min": round(min(r["k_us"]), 2),
+                          "kernel_us_max": round(max(r["k_us"]), 2),
+                          "step_us_min": round(min(r["step_us"]), 2), "step_us_max": round(max(r["step_us"]), 2),
                           "kernel_csr_GBs": round(kb / km / 1e3, 1), "step_us_med": round(sm, 2),
                           "step_us_med_with_events": round(float(np.median(r["step_us_events"])), 2)
                           if r["step_us_events"] else None,

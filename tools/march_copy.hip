@@ -6,6 +6,8 @@
 //
 // One JSON line per (pattern, plane runs): GB/s = 2 * n * 16 B / kernel time.
 // `march_copy N values`: the value march's streams instead (k_vmarch; GB/s over 64 B per row).
+// `march_copy N values serpentine [runs] [rounds]`: the 2-line full-step probe with every second launch
+// marching down, against all launches marching up, each with nontemporal and plain pair stores.
 // `march_copy N kuhn`: the P1 Kuhn march's streams (k_kmarch; GB/s over 96 B per row).
 // `march_copy N box`: the C5 Chebyshev step's streams as a plain copy (k_boxcopy; 1152 B per row).
 //   linear     grid-stride 16-B copy (the reference rate)
@@ -375,7 +377,10 @@ __global__ __launch_bounds__(kThreads, W) void k_vabl(int n, int D, int nx, int 
 // (round 6 probe): lane = x, the wave's lines y0 = 2 ly and y0 + 1, so the +nx operand of line y0 and
 // the -nx operand and mirrored -nx value of line y0 + 1 are the other line's registers; only line
 // y0 - 1's operand and mirrored value and line y0 + 2's operand are gathered (half the gathers).
-template <int W>
+// DOWN: every plane run marched from its last plane to its first (the streams of the downward march:
+// the pair of the plane below loaded, the one above carried; the (+D, 0) value pair of the plane below
+// loaded, the plane's own carried); TS: the output pairs with plain instead of nontemporal stores.
+template <int W, bool DOWN = false, bool TS = false>
 __global__ __launch_bounds__(kThreads, W) void k_vabl2(int n, int D, int nx, int ncol, int nseg, int nplanes,
                                                        const dpair *__restrict__ P, const dpair *__restrict__ V,
                                                        dpair *__restrict__ Q, double *__restrict__ sums, double c)
@@ -389,16 +394,26 @@ __global__ __launch_bounds__(kThreads, W) void k_vabl2(int n, int D, int nx, int
   const int lastrow = n - 1;
   auto cl = [&](int g) { return g < 0 ? 0 : (g > lastrow ? lastrow : g); };
   const int line0 = 2 * (col2 / xc);
-  int w = line0 * nx + (col2 % xc) * 64 + lane + z0 * D;  // row of line y0; line y0 + 1 at w + nx
+  constexpr int DIR = DOWN ? -1 : 1;  // the plane loaded each iteration lies DIR planes away
+  int w = line0 * nx + (col2 % xc) * 64 + lane + (DOWN ? z1 - 1 : z0) * D;  // row of line y0; line y0 + 1 at w + nx
   dpair cur0 = P[cl(w)], cur1 = P[cl(w + nx)];
-  dpair prev0 = P[cl(w - D)], prev1 = P[cl(w + nx - D)];
+  dpair prev0 = P[cl(w - DIR * D)], prev1 = P[cl(w + nx - DIR * D)];
+  dpair av0 = dpair{0.0, 0.0}, av1 = dpair{0.0, 0.0};
+  if (DOWN)
+  {
+    av0 = __builtin_nontemporal_load(V + w);
+    av1 = __builtin_nontemporal_load(V + w + nx);
+  }
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
   auto uk = [&](dpair p) { return p.x - c * p.y; };
-  for (int z = z0; z < z1; ++z, w += D)
+  for (int z = z0; z < z1; ++z, w += DIR * D)
   {
-    const dpair pd0 = P[cl(w + D)], pd1 = P[cl(w + nx + D)];
-    const dpair a0 = __builtin_nontemporal_load(V + w), b0 = V[n + w];
-    const dpair a1 = __builtin_nontemporal_load(V + w + nx), b1 = V[n + w + nx];
+    const dpair pd0 = P[cl(w + DIR * D)], pd1 = P[cl(w + nx + DIR * D)];
+    const dpair l0 = __builtin_nontemporal_load(V + cl(DOWN ? w - D : w)), b0 = V[n + w];
+    const dpair l1 = __builtin_nontemporal_load(V + cl(DOWN ? w + nx - D : w + nx)), b1 = V[n + w + nx];
+    const dpair a0 = DOWN ? dpair{av0.x, l0.x} : l0, a1 = DOWN ? dpair{av1.x, l1.x} : l1;
+    av0 = l0;
+    av1 = l1;
     const dpair u = P[cl(w - nx)], v = P[cl(w + 2 * nx)];
     dpair e0 = dpair{0.0, 0.0}, e1 = dpair{0.0, 0.0};
     if (lane == 0 || lane == 63)
@@ -434,8 +449,16 @@ __global__ __launch_bounds__(kThreads, W) void k_vabl2(int n, int D, int nx, int
     };
     const dpair o0 = row(a0, b0, prev0, mnx0, uk(u), m1e0, e0, vc0, vc1, pd0, cur0);
     const dpair o1 = row(a1, b1, prev1, b0.y, vc0, m1e1, e1, vc1, uk(v), pd1, cur1);
-    __builtin_nontemporal_store(o0, Q + w);
-    __builtin_nontemporal_store(o1, Q + w + nx);
+    if (TS)
+    {
+      Q[w] = o0;
+      Q[w + nx] = o1;
+    }
+    else
+    {
+      __builtin_nontemporal_store(o0, Q + w);
+      __builtin_nontemporal_store(o1, Q + w + nx);
+    }
     prev0 = cur0;
     prev1 = cur1;
     cur0 = pd0;
@@ -707,6 +730,64 @@ int main(int argc, char **argv)
       const int items = ncol * nseg, G = (items + kW - 1) / kW;
       outv("values_march_pp", nseg, time([&] { k_vmarch<false, false><<<G, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst()); }));
       outv("values_march_g_pp", nseg, time([&] { k_vmarch<false, true><<<G, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst()); }));
+    }
+    if (argc > 3 && std::string(argv[3]) == "serpentine")
+    {
+      // Direction flip of the full-step 2-line probe (k_vabl2<5>) at `runs` plane runs, ping-pong: up/up against
+      // up/down (every second launch marches its runs from the last plane down, so it starts on what the
+      // launch before it touched last), each with nontemporal and with plain pair stores.  The arms
+      // alternate round by round in one process; per arm the median over rounds and the spread (max - min).
+      double *sums;
+      const int nseg = argc > 4 ? std::atoi(argv[4]) : 2, rounds = argc > 5 ? std::atoi(argv[5]) : 7;
+      const int G2 = ((ncol / 2) * nseg + kW - 1) / kW;
+      CK(hipMalloc(&sums, (size_t)(3 * G2 + 64) * sizeof(double)));
+      CK(hipMemset(sums, 0, (size_t)(3 * G2 + 64) * sizeof(double)));
+      // (arms 4 / 5: every launch marches down -- what the direction itself costs, no reuse between launches)
+      constexpr int kArms = 6;
+      const char *names[kArms] = {"serp_upup_nt",      "serp_updown_nt",  "serp_upup_plain",
+                                  "serp_updown_plain", "serp_downdown_nt", "serp_downdown_plain"};
+      std::vector<double> us[kArms];
+      for (int r = 0; r < rounds; ++r)
+        for (int arm = 0; arm < kArms; ++arm)
+        {
+          const bool alt = arm & 1, ts = arm == 2 || arm == 3 || arm == 5;
+          rep = 0;  // every arm starts on P
+          const double t = time([&] {
+            const bool down = arm >= 4 || (alt && (rep & 1));
+            if (ts)
+            {
+              if (down)
+                k_vabl2<5, true, true><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
+              else
+                k_vabl2<5, false, true><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
+            }
+            else
+            {
+              if (down)
+                k_vabl2<5, true, false><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
+              else
+                k_vabl2<5, false, false><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
+            }
+          });
+          us[arm].push_back(t);
+          std::printf("{\"pattern\": \"%s\", \"N\": %d, \"runs\": %d, \"round\": %d, \"us\": %.2f, \"GBs\": %.1f}\n",
+                      names[arm], N, nseg, r, t, 4.0 * n * sizeof(dpair) / t * 1e-3);
+          std::fflush(stdout);
+        }
+      for (int arm = 0; arm < kArms; ++arm)
+      {
+        std::sort(us[arm].begin(), us[arm].end());
+        std::printf("{\"pattern\": \"%s\", \"N\": %d, \"runs\": %d, \"rounds\": %d, \"us_med\": %.2f, "
+                    "\"us_min\": %.2f, \"us_max\": %.2f, \"spread_us\": %.2f}\n",
+                    names[arm], N, nseg, rounds, us[arm][us[arm].size() / 2], us[arm].front(), us[arm].back(),
+                    us[arm].back() - us[arm].front());
+      }
+      CK(hipGetLastError());
+      CK(hipFree(sums));
+      CK(hipFree(V));
+      CK(hipFree(P));
+      CK(hipFree(Q));
+      return 0;
     }
     if (argc > 3 && std::string(argv[3]) == "ablation")
     {
