@@ -1947,6 +1947,22 @@ extern "C" int eig_lanczos_info(eig_lanczos_t ws, int *steps, int *launches)
   });
 }
 
+extern "C" int eig_lanczos_pairs(eig_lanczos_t ws, double *pairs_host, int64_t rows)
+{
+  return guard(ws ? ws->A->ctx : nullptr, [&] {
+    EIG_CHECK(ws && pairs_host, EIG_ERR_ARG, "eig_lanczos_pairs: null argument");
+    EIG_CHECK(ws->fused && !ws->pipe, EIG_ERR_ARG, "eig_lanczos_pairs: the fused step's workspace only");
+    const eig_mat_s &A = *ws->A;
+    EIG_CHECK(A.br == 1 && A.bc == 1 && rows == A.nb_rows, EIG_ERR_SHAPE, "eig_lanczos_pairs: the owned rows of a 1x1 matrix");
+    eig_ctx_t ctx = A.ctx;
+    EIG_HIP(hipSetDevice(ctx->device));
+    EIG_HIP(hipStreamSynchronize(ctx->stream));
+    // the pairs the last launch wrote: launch L reads B[L & 1]
+    EIG_HIP(hipMemcpy(pairs_host, ws->B[ws->L & 1]->d() + 2 * A.own_offset, 2 * rows * sizeof(double),
+                      hipMemcpyDeviceToHost));
+  });
+}
+
 extern "C" int eig_lanczos_destroy(eig_lanczos_t ws)
 {
   if (!ws) return EIG_OK;

@@ -384,6 +384,7 @@ void launch_fused_tail(const LanczosState &st, int L, hipStream_t s);
 bool march_geometry(const eig_mat_s &A, i64 &D, int chunk = 64);
 bool march_split_active(const eig_mat_s &A);
 int march_variant(const eig_mat_s &A, bool fused);
+int march_pipe(const eig_mat_s &A);  // 1: a whole-matrix fused launch takes the pipelined 2-line body
 extern const i32 kMarchInteriorTag;
 // a2 SpMM (kernels_cpp.hh:626-657) on the band-image plane march for 1x1 matrices whose band
 // qualifies; false (nothing launched) otherwise.  X, Y: window-layout multivectors, m % 8 == 0.

@@ -17,6 +17,9 @@
 #include "reduce_dev.h"
 #include "xch_dev.h"
 
+#include <atomic>
+#include <type_traits>
+
 namespace eigmi {
 
 constexpr int kWaves = kStreamThreads / 64;
@@ -1311,6 +1314,10 @@ struct MarchPlan {
   // (march_rows_geo2_2l<DOWN>); wave-uniform, a kernel argument -- a launch captured into a graph replays
   // its own direction
   int down;
+  // the fused launches of variants 22 / 23: 1 = the body that loads every plane through LDS, one plane ahead
+  // (march_rows_geo2_2l<DOWN, PIPE>; the launch then carries kMarchPipeLds bytes of dynamic LDS); wave-uniform,
+  // a kernel argument like `down`
+  int pipe;
 };
 // store helper of the geo2 epilogues: temporal when the plan says the vectors fit the MALL
 template <class T>
@@ -1693,8 +1700,73 @@ constexpr bool kMarch2lSerpentine = true;
 constexpr bool march_down_variant(int uni) { return uni == 22 || uni == 23; }  // (24 spills marching upward alone)
 template <int UNI>
 constexpr bool kMarchDownBody = march_down_variant(UNI);
+// variants whose fused kernel also holds the pipelined bodies (PIPE below; 24 keeps the plain body)
+constexpr bool march_pipe_variant(int uni) { return uni == 22 || uni == 23; }
+template <int UNI>
+constexpr bool kMarchPipeBody = march_pipe_variant(UNI);
 
-template <bool DOWN, class X, class EPI, class PRE>
+// PIPE (the fused launches of variants 22 / 23 where MarchPlan::pipe is set; DESIGN section 4e "pipeline"): with
+// one wave per SIMD nothing else issues loads while the wave does a plane's arithmetic, and the registers
+// hold one plane of loads, so every iteration of the bodies below pays the memory latency and the arithmetic
+// one after the other.  Here every loop load is an LDS-DMA (buffer_load ... lds: no register destination)
+// issued ONE PLANE AHEAD into the other of two LDS buffers of the wave; a buffer is kMarchPipeRegions
+// lane-linear regions of 64 x 16 B, one region per load, wave-private -- no barrier.  Iteration z issues plane
+// z +- 1's 13 DMAs, waits with one counted vmcnt that retires plane z's (the new 13 and the previous plane's
+// 2 stores stay in flight), reads its operands back (ds_read_b128, waited for inside the reading statement,
+// so the buffer is free before the iteration after refills it) and does the arithmetic of the plain body in
+// its order.  A DMA's address is always in range: where the plain body reads an exact zero through a
+// zero-record descriptor or an out-of-range offset (grid faces, the planes below the first and above the
+// last), the DMA reads the lane's own row instead and the zero is selected after the LDS read (the
+// conditions are wave- or lane-uniform) -- the same +0 operands, so every row is bitwise the plain body's,
+// and a lane adds its rows into the three sums in the same order: alpha and beta are bitwise too.  The 8-B
+// loads (line y0 - 1's mirrored value, lane 0's mirrored -1 values) are 16-B DMAs of the pair that holds them.
+// Measured at 256^3, 7 interleaved rounds (profiles/r08_pipe_sweep.jsonl): 180.3 us against 185.1
+// for the plain bodies (max - min 0.8) -- the gain is the downward launches' (all-down 189.3 against 195.4;
+// all-up 189.8 either way: the plain upward body already overlapped most of its products with the loads).
+constexpr int kMarchPipeRegions = 13;
+constexpr unsigned kMarchPipeBuf = kMarchPipeRegions * 1024u;  // one plane of one wave
+constexpr unsigned kMarchPipeLds = kWaves * 2 * kMarchPipeBuf;  // dynamic LDS of a pipelined launch
+constexpr int kMaxPipeDevices = 64;  // device indices whose kernels launch_lanczos_fused has raised to it
+typedef __attribute__((address_space(3))) char lds_char;
+template <int AUX>
+__device__ __forceinline__ void bdma(__amdgpu_buffer_rsrc_t r, unsigned off, lds_char *l)
+{
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, l, 16, (int)off, 0, 0, AUX);
+}
+// LDS reads of a plane's operands (a: the lane's slot of region 0) and the wait for them, in one statement each:
+// the compiler neither sees an LDS-DMA's write nor counts these reads.  Three statements, the operands that
+// shrink to their values first, so that a plane's 13 operands are never all in registers at once.
+// regions 6, 7, 9, 10 (whole pairs), the .y of region 8's pair, the .x of the pairs of regions 11 and 12
+__device__ __forceinline__ void lds_read_near(unsigned a, dpair &r6, dpair &r7, dpair &r9, dpair &r10, double &y8,
+                                              double &x11, double &x12)
+{
+  asm volatile("ds_read_b128 %0, %7 offset:6144\n\tds_read_b128 %1, %7 offset:7168\n\t"
+               "ds_read_b128 %2, %7 offset:9216\n\tds_read_b128 %3, %7 offset:10240\n\t"
+               "ds_read_b64 %4, %7 offset:8200\n\tds_read_b64 %5, %7 offset:11264\n\t"
+               "ds_read_b64 %6, %7 offset:12288\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(r6), "=&v"(r7), "=&v"(r9), "=&v"(r10), "=&v"(y8), "=&v"(x11), "=&v"(x12)
+               : "v"(a)
+               : "memory");
+}
+// regions 4, 5, 0, 1
+__device__ __forceinline__ void lds_read_mid(unsigned a, dpair &r4, dpair &r5, dpair &r0, dpair &r1)
+{
+  asm volatile("ds_read_b128 %0, %4 offset:4096\n\tds_read_b128 %1, %4 offset:5120\n\tds_read_b128 %2, %4\n\t"
+               "ds_read_b128 %3, %4 offset:1024\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(r4), "=&v"(r5), "=&v"(r0), "=&v"(r1)
+               : "v"(a)
+               : "memory");
+}
+// regions 2, 3
+__device__ __forceinline__ void lds_read_far(unsigned a, dpair &r2, dpair &r3)
+{
+  asm volatile("ds_read_b128 %0, %2 offset:2048\n\tds_read_b128 %1, %2 offset:3072\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(r2), "=&v"(r3)
+               : "v"(a)
+               : "memory");
+}
+
+template <bool DOWN, bool PIPE = false, class X, class EPI, class PRE>
 __device__ __forceinline__ void march_rows_geo2_2l(const SellB1 &A, const MarchPlan &mp, i64 own, int lane, int wave,
                                                    X x, EPI &epi, PRE &pre)
 {
@@ -1722,6 +1794,237 @@ __device__ __forceinline__ void march_rows_geo2_2l(const SellB1 &A, const MarchP
   const SymImg &S = A.sym;
   const dpair *P01 = reinterpret_cast<const dpair *>(mp.pack), *P23 = P01 + S.ld;
   const bool le = lane == 0 && x0 > 0;  // lane 0's mirrored -1 value (row x0 - 1) exists
+  if constexpr (PIPE)
+  {
+    static_assert(SZ == sizeof(dpair), "the pipelined body marches the fused step's pair vector");
+    extern __shared__ char march_pipe_lds[];
+    lds_char *const Lw = (lds_char *)march_pipe_lds + (unsigned)wave * (2 * kMarchPipeBuf);
+    const unsigned ra0 = (unsigned)(size_t)Lw + (unsigned)lane * 16u;  // the lane's slot of region 0, buffer 0
+    // the pack through one descriptor too, its second pair array ldb bytes on (the plan admits the body only
+    // where these byte offsets fit 32 bits)
+    const unsigned ldb = (unsigned)S.ld * 16u;
+    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<dpair *>(P01), 0, (int)(2u * ldb), 0x00020000);
+    const bool edge = lane == 0 || lane == 63;
+    // offsets of the operands that may be missing: the lane's own row (0) where they are.  eo: the row across
+    // the wave edge (lanes 0 and 63; 0 elsewhere too); lo: the row before lane 0's (wave-uniform: only lane 0's
+    // mirrored -1 value is ever used, lane_shift_or keeps it for the lane without a source)
+    const bool lok = x0 > 0;
+    const unsigned eo = lane == 0 ? (lok ? 0u - SZ : 0u) : (lane == 63 && x0 + 64 < gx ? SZ : 0u), lo = lok ? 0u - SZ : 0u;
+    const unsigned no = has_n ? dnb : 0u, qo = has_q ? dqb : 0u;
+    // regions: 0, 1 the far (+-D) operands of the two lines; 2, 3 the (+D, 0) values (xfar / pfar: the byte
+    // offsets of the plane they come from); 4, 5 the (+1, +nx) values; 6, 7 the operands of lines y0 - 1,
+    // y0 + 2; 8 line y0 - 1's (+1, +nx) values; 9, 10 the x-edge operands (lanes 0 and 63); 11, 12 the
+    // (+1, +nx) values of the rows before lane 0's
+    auto issue = [&](unsigned v, unsigned xfar, unsigned pfar, lds_char *L) {
+      bdma<0>(rs, v + xfar, L);
+      bdma<0>(rs, v + nxb + xfar, L + 1024);
+      if (mp.cache & 2)
+      {
+        bdma<0>(rp, v + pfar, L + 2 * 1024);
+        bdma<0>(rp, v + nxb + pfar, L + 3 * 1024);
+      }
+      else
+      {
+        bdma<2>(rp, v + pfar, L + 2 * 1024);
+        bdma<2>(rp, v + nxb + pfar, L + 3 * 1024);
+      }
+      bdma<0>(rp, v + ldb, L + 4 * 1024);
+      bdma<0>(rp, v + ldb + nxb, L + 5 * 1024);
+      bdma<0>(rs, v + no, L + 6 * 1024);
+      bdma<0>(rs, v + nxb + qo, L + 7 * 1024);
+      bdma<0>(rp, v + ldb + no, L + 8 * 1024);
+      if (edge)
+      {
+        bdma<0>(rs, v + eo, L + 9 * 1024);
+        bdma<0>(rs, v + nxb + eo, L + 10 * 1024);
+      }
+      if (lane == 0)
+      {
+        bdma<0>(rp, v + ldb + lo, L + 11 * 1024);
+        bdma<0>(rp, v + ldb + nxb + lo, L + 12 * 1024);
+      }
+    };
+    const dpair zero = dpair{0.0, 0.0};
+    // "the operand exists" = its offset is not 0, compared per plane: the kernel is at its scalar-register
+    // limit, and a condition mask kept over the loop is two registers that then spill
+    auto eok = [&] {  // the lane's row across the wave edge
+      unsigned t = eo;
+      asm volatile("" : "+v"(t));
+      return t != 0u;
+    };
+    auto nz = [](unsigned t) {  // (wave-uniform offsets)
+      t = __builtin_amdgcn_readfirstlane(t);
+      asm volatile("" : "+s"(t));
+      return t != 0u;
+    };
+    unsigned bo = 0;  // byte offset of the buffer that holds the plane at hand
+    if constexpr (DOWN)
+    {
+      auto row = [&](double amD, double vmD, double an, double vn, double am, double vl, double a0, double vc, double a1,
+                     double vr, double aq, double vq, double prodD) {
+        double acc = 0.0;
+        acc += amD * vmD;
+        acc += an * vn;
+        acc += am * vl;
+        acc += a0 * vc;
+        acc += a1 * vr;
+        acc += aq * vq;
+        acc += prodD;
+        return acc;
+      };
+      w += (z1 - 1 - z0) * D;
+      vo = (unsigned)w * SZ;
+      const int gbot = -mp.gz0;  // the rank's index of global plane 0: plane z has a plane below when z > gbot
+      issue(vo, z1 - 1 > gbot ? 0u - Db : 0u, z1 - 1 > gbot ? 0u - Db : 0u, Lw);
+      const bool above = z1 + mp.gz0 < mp.gz;
+      raw pu0{}, pu1{};
+      if (above)
+      {
+        bload(rs, vo + Db, pu0);
+        bload(rs, vo + nxb + Db, pu1);
+      }
+      dpair p0a = (mp.cache & 2) ? P01[w] : __builtin_nontemporal_load(P01 + w);
+      dpair p1a = (mp.cache & 2) ? P01[w + gx] : __builtin_nontemporal_load(P01 + w + gx);
+      raw c0, c1;
+      bload(rs, vo, c0);
+      bload(rs, vo + nxb, c1);
+      const bool go = pre(x);
+      // every load so far lands here: a later use of an ordinary load would drain the DMAs in flight with it
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(pu0), "+v"(pu1), "+v"(p0a), "+v"(p1a), "+v"(c0), "+v"(c1)::"memory");
+      if (!go) return;
+      double a00 = p0a.y, a01 = p1a.y;
+      double pD0 = p0a.x * (above ? x.val(pu0) : 0.0), pD1 = p1a.x * (above ? x.val(pu1) : 0.0);
+      for (int z = z1 - 1; z >= z0; --z)
+      {
+        // in order on the counter: this plane's 13 DMAs, the previous plane's 2 stores, the next plane's 13 DMAs
+        if (z > z0)
+        {
+          const unsigned far = z - 1 > gbot ? 0u - Db : 0u;
+          issue(vo - Db, far, far, Lw + (bo ^ kMarchPipeBuf));
+          asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
+        }
+        else
+          asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        dpair m0, m1, q0a, q1a, p0b, p1b, xn0, xq1, eg0, eg1;
+        double any, ae0x, ae1x;
+        lds_read_near(ra0 + bo, xn0, xq1, eg0, eg1, any, ae0x, ae1x);
+        const bool hn = nz(no), lk = nz(lo);
+        if (!hn) xn0 = zero;
+        if (!nz(qo)) xq1 = zero;
+        if (!eok()) eg0 = eg1 = zero;
+        const double an0 = hn ? any : 0.0;
+        const double ae0 = lk ? ae0x : 0.0, ae1 = lk ? ae1x : 0.0;
+        double vn0 = x.val(xn0), vq1 = x.val(xq1), ve0 = x.val(eg0), ve1 = x.val(eg1);
+        asm volatile("" : "+v"(vn0), "+v"(vq1), "+v"(ve0), "+v"(ve1));  // (the pairs are dead before the next reads)
+        lds_read_mid(ra0 + bo, p0b, p1b, m0, m1);
+        lds_read_far(ra0 + bo, q0a, q1a);
+        if (!(z > gbot)) m0 = m1 = q0a = q1a = zero;
+        const double vc0 = x.val(c0), vc1 = x.val(c1);
+        const double acc0 = row(q0a.x, x.val(m0), an0, vn0, lane_shift_or<false>(p0b.x, ae0),
+                                lane_shift_or<false>(vc0, ve0), a00, vc0, p0b.x, lane_shift_or<true>(vc0, ve0), p0b.y,
+                                vc1, pD0);
+        const double acc1 = row(q1a.x, x.val(m1), p0b.y, vc0, lane_shift_or<false>(p1b.x, ae1),
+                                lane_shift_or<false>(vc1, ve1), a01, vc1, p1b.x, lane_shift_or<true>(vc1, ve1), p1b.y,
+                                vq1, pD1);
+        epi(w - own32, w, acc0, c0);
+        epi(w + gx - own32, w + gx, acc1, c1);
+        pD0 = q0a.x * vc0;
+        pD1 = q1a.x * vc1;
+        a00 = q0a.y;
+        a01 = q1a.y;
+        c0 = m0;
+        c1 = m1;
+        w -= D;
+        vo -= Db;
+        bo ^= kMarchPipeBuf;
+      }
+    }
+    else
+    {
+      const int gtop = mp.gz - 1 - mp.gz0;  // the rank's index of the top global plane: plane z has one above when z < gtop
+      issue(vo, z0 < gtop ? Db : 0u, 0u, Lw);
+      double amD0 = 0.0, amD1 = 0.0;
+      raw pm0{}, pm1{};
+      if (zg0 > 0)
+      {
+        bload(rs, vo - Db, pm0);
+        bload(rs, vo + nxb - Db, pm1);
+        amD0 = P01[w - D].x;
+        amD1 = P01[w + gx - D].x;
+      }
+      raw c0, c1;
+      bload(rs, vo, c0);
+      bload(rs, vo + nxb, c1);
+      const bool go = pre(x);
+      // every load so far lands here: a later use of an ordinary load would drain the DMAs in flight with it
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(pm0), "+v"(pm1), "+v"(amD0), "+v"(amD1), "+v"(c0), "+v"(c1)::"memory");
+      if (!go) return;
+      double pmv0 = zg0 > 0 ? x.val(pm0) : 0.0, pmv1 = zg0 > 0 ? x.val(pm1) : 0.0;
+      for (int z = z0; z < z1; ++z)
+      {
+        // in order on the counter: this plane's 13 DMAs, the previous plane's 2 stores, the next plane's 13 DMAs
+        if (z + 1 < z1)
+        {
+          issue(vo + Db, z + 1 < gtop ? Db : 0u, 0u, Lw + (bo ^ kMarchPipeBuf));
+          asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
+        }
+        else
+          asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        dpair d0, d1, p0a, p1a, p0b, p1b, xn0, xq1, eg0, eg1;
+        double any, ae0x, ae1x;
+        lds_read_near(ra0 + bo, xn0, xq1, eg0, eg1, any, ae0x, ae1x);
+        const bool hn = nz(no), lk = nz(lo);
+        if (!hn) xn0 = zero;
+        if (!nz(qo)) xq1 = zero;
+        if (!eok()) eg0 = eg1 = zero;
+        const double an0 = hn ? any : 0.0;
+        const double ae0 = lk ? ae0x : 0.0, ae1 = lk ? ae1x : 0.0;
+        double vn0 = x.val(xn0), vq1 = x.val(xq1), ve0 = x.val(eg0), ve1 = x.val(eg1);
+        asm volatile("" : "+v"(vn0), "+v"(vq1), "+v"(ve0), "+v"(ve1));  // (the pairs are dead before the next reads)
+        lds_read_mid(ra0 + bo, p0b, p1b, d0, d1);
+        lds_read_far(ra0 + bo, p0a, p1a);
+        if (!(z < gtop)) d0 = d1 = zero;
+        const double vc0 = x.val(c0), vc1 = x.val(c1);
+        double acc0 = 0.0, acc1 = 0.0;
+        {
+          const double ve = ve0;
+          const double vl = lane_shift_or<false>(vc0, ve), vr = lane_shift_or<true>(vc0, ve);
+          const double am = lane_shift_or<false>(p0b.x, ae0);
+          acc0 += amD0 * pmv0;
+          acc0 += an0 * vn0;
+          acc0 += am * vl;
+          acc0 += p0a.y * vc0;
+          acc0 += p0b.x * vr;
+          acc0 += p0b.y * vc1;
+          acc0 += p0a.x * x.val(d0);
+        }
+        {
+          const double ve = ve1;
+          const double vl = lane_shift_or<false>(vc1, ve), vr = lane_shift_or<true>(vc1, ve);
+          const double am = lane_shift_or<false>(p1b.x, ae1);
+          acc1 += amD1 * pmv1;
+          acc1 += p0b.y * vc0;
+          acc1 += am * vl;
+          acc1 += p1a.y * vc1;
+          acc1 += p1b.x * vr;
+          acc1 += p1b.y * vq1;
+          acc1 += p1a.x * x.val(d1);
+        }
+        epi(w - own32, w, acc0, c0);
+        epi(w + gx - own32, w + gx, acc1, c1);
+        pmv0 = vc0;
+        pmv1 = vc1;
+        amD0 = p0a.x;
+        amD1 = p1a.x;
+        c0 = d0;
+        c1 = d1;
+        w += D;
+        vo += Db;
+        bo ^= kMarchPipeBuf;
+      }
+    }
+    return;
+  }
   if constexpr (DOWN)
   {
     // one row's sum: the seven products in ascending-offset order; the +D product comes in already rounded
@@ -2158,6 +2461,16 @@ __device__ __forceinline__ void march_rows(const SellB1 &A, const MarchPlan &mp,
   }
   else if constexpr (kTraits<UNI>.family == kMarchGeo2L2)
   {
+    // the pipelined bodies: the fused step (the pair vector) of the variants kept at 96 registers
+    if constexpr (kMarchPipeBody<UNI> && std::is_same<X, XPair>::value)
+      if (mp.pipe)
+      {
+        if (mp.down)
+          march_rows_geo2_2l<true, true>(A, mp, own, lane, wave, x, epi, pre);
+        else
+          march_rows_geo2_2l<false, true>(A, mp, own, lane, wave, x, epi, pre);
+        return;
+      }
     if constexpr (kMarchDownBody<UNI>)
       if (mp.down)
       {
@@ -3182,6 +3495,22 @@ static MarchPlan march_plan(const eig_mat_s &A, int mode, i64 zb = 0, i64 ze = -
   // EIG_TUNE_CACHE 16: every launch of the 2-line variants with a downward body marches down (eig_mv and the
   // classic K1 too, when tuned onto them).  The fused step's alternation (neither bit, or both): launch_lanczos_fused
   mp.down = march_down_variant(uni) && (A.tune_cache & 24) == 16;
+  // the pipelined body (march_rows_geo2_2l<DOWN, PIPE>) takes kMarchPipeLds of LDS per workgroup -- one
+  // workgroup per CU -- so it is on only where the launch has no more than that anyway: the two-run plan on
+  // wide planes.  EIG_TUNE_CACHE 32: never; 64: wherever the body can run (tests reach small grids with it).
+  // (The pack goes through one buffer descriptor there: 32-bit byte offsets over both of its pair arrays.)
+  // Short runs pay the pipeline's fill (a first plane that overlaps nothing) for fewer planes: 256^2 slabs,
+  // 7 interleaved rounds, kernel medians pipelined / plain (profiles/r08_pipe_sweep.jsonl): 32 planes 28.2 /
+  // 26.8 us, 64 planes 46.3 / 44.9, 128 planes 91.1 / 96.2, 256^3 180.3 / 185.1 -- so where the variant is
+  // the automatic choice the body is on from EIG_MARCH_PIPE_MIN_ROWS owned rows (like EIG_MARCH_2L_MIN_ROWS, the
+  // threshold gates the automatic choice only: a variant asked for by EIG_TUNE_MARCH_PREFETCH takes the
+  // plan's rule as it is).
+  {
+    const i64 wgs = (items_per_run * nseg + kWaves - 1) / kWaves;
+    const bool can = fused && march_pipe_variant(uni) && A.sym_ld * 32 < (i64(1) << 32);
+    const bool pays = A.tune_march_prefetch != 0 || A.nb_rows >= EIG_MARCH_PIPE_MIN_ROWS;
+    mp.pipe = can && !(A.tune_cache & 32) && ((A.tune_cache & 64) || (wide_pack && wgs <= A.ctx->num_cu && pays));
+  }
   // line groups (MarchTraits::line_groups, on grids of whole 64-x runs and 4-line groups)
   mp.lines = A.tune_march_lines == 4 && T.line_groups && mp.gx % 64 == 0 &&
                      mp.gx > 0 && mp.gy % 4 == 0 && (i64)mp.gx * mp.gy == D
@@ -3201,6 +3530,14 @@ int march_variant(const eig_mat_s &A, bool fused)
   if (A.br != 1 || A.bc != 1) return -1;
   const MarchPlan mp = march_plan(A, image_mode(A), 0, -1, fused);
   return mp.nseg > 0 ? mp.uni : -1;
+}
+
+// eig_mat_info.march_pipe: a whole-matrix fused launch takes the pipelined body (MarchPlan::pipe)
+int march_pipe(const eig_mat_s &A)
+{
+  if (A.br != 1 || A.bc != 1) return 0;
+  const MarchPlan mp = march_plan(A, image_mode(A), 0, -1, true);
+  return mp.nseg > 0 ? mp.pipe : 0;
 }
 
 const i32 kMarchInteriorTag = 0;
@@ -3393,8 +3730,25 @@ void launch_lanczos_fused(const eig_mat_s &A, const double *P, double *Pout, con
       if (march_down_variant(mp.uni) && ((A.tune_cache & 24) == 24 || (kMarch2lSerpentine && !(A.tune_cache & 24))))
         mp.down = fl.L & 1;
       march_launch(MarchDispatch{}, A, mode, mp.uni, [&](auto mt, auto span1, auto uni) {
+        if constexpr (march_pipe_variant(uni()))
+        {
+          // the pipelined body's LDS is past the 64 KiB a kernel gets unasked: raise the kernel's limit once
+          // per device
+          static std::atomic<bool> raised[kMaxPipeDevices];
+          const int dev = A.ctx->device;
+          EIG_CHECK(!mp.pipe || (dev >= 0 && dev < kMaxPipeDevices), EIG_ERR_ARG, "pipelined march: device index");
+          if (mp.pipe && !raised[dev].load(std::memory_order_acquire))
+          {
+            EIG_HIP(hipFuncSetAttribute(
+                reinterpret_cast<const void *>(&k_lanczos_fused_march<decltype(mt), span1(), uni()>),
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMarchPipeLds));
+            raised[dev].store(true, std::memory_order_release);
+          }
+        }
+        else
+          mp.pipe = 0;
         hipLaunchKernelGGL((k_lanczos_fused_march<decltype(mt), span1(), uni()>), dim3(march_grid(mp)),
-                           dim3(kStreamThreads), 0, s, A.nb_rows, A.own_offset, sell_b1(A), mp,
+                           dim3(kStreamThreads), mp.pipe ? kMarchPipeLds : 0, s, A.nb_rows, A.own_offset, sell_b1(A), mp,
                            reinterpret_cast<const dpair *>(P), reinterpret_cast<dpair *>(Pout), fa, out, red.partials,
                            red.ticket(ticket));
       });

@@ -75,7 +75,7 @@ class _MatInfo(ctypes.Structure):
                [(k, ctypes.c_int64) for k in ("halo_recv", "halo_send", "device_bytes", "stencil_slices",
                                               "rows_per_lane", "sym_offsets", "sym_arrays",
                                               "sym_mask_bytes", "sym_uniform", "sym_geo",
-                                              "march_variant", "march_variant_mv")]
+                                              "march_variant", "march_variant_mv", "march_pipe")]
 
 
 class BlockTiming(ctypes.Structure):
@@ -177,6 +177,7 @@ SIGNATURES = {
     "eig_lanczos_tridiag": (_int, [_vp, ctypes.POINTER(_int), _vp, _vp]),
     "eig_lanczos_destroy": (_int, [_vp]),
     "eig_lanczos_info": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "eig_lanczos_pairs": (_int, [_vp, _vp, _i64]),
     "eig_lanczos_capture": (_int, [_vp, _int, _int, ctypes.POINTER(_int)]),
     "eig_lanczos_ws_info": (_int, [_vp, ctypes.POINTER(_int), ctypes.c_char_p, _int, ctypes.POINTER(_i64)]),
     "eig_lanczos_replay": (_int, [_vp, ctypes.POINTER(Timing)]),
@@ -755,6 +756,12 @@ class LanczosWorkspace:
         k, L = _int(0), _int(0)
         self.A.ctx.check(lib.eig_lanczos_info(self.h, ctypes.byref(k), ctypes.byref(L)))
         return k.value, L.value
+
+    def pairs(self):
+        """The (t, u) pairs the fused step's last launch wrote for the owned rows: an (n, 2) array."""
+        out = np.zeros((self.A.n, 2))
+        self.A.ctx.check(lib.eig_lanczos_pairs(self.h, _np_ptr(out), self.A.n))
+        return out
 
     def tridiag(self):
         k = _int(0)

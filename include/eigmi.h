@@ -229,6 +229,8 @@ typedef struct eig_mat_info {
                              values at 4 / 5 waves per SIMD, 20 the pack with the line exchange in
                              LDS); 13, 17 and 21 are unused */
   int64_t march_variant_mv; /* the same for eig_mv (BCRSMatrix::mv) */
+  int64_t march_pipe;     /* 1: that fused launch (variants 22 / 23) loads every plane through LDS, one
+                             plane ahead (EIG_TUNE_CACHE bits 5 / 6) */
 } eig_mat_info;
 int eig_mat_get_info(eig_mat_t mat, eig_mat_info *info);
 
@@ -279,7 +281,13 @@ enum { EIG_TUNE_MARCH_RUNS = 1, EIG_TUNE_BOX_SEGS = 2, EIG_TUNE_MARCH_PREFETCH =
  * to its first -- eig_mv and the classic step too where EIG_TUNE_MARCH_PREFETCH 16 / 17 routes them
  * there (tests and A/B only); both bits (24) = fused launches alternate, downward when the launch
  * index is odd, whatever the built-in default is.  Neither bit: the default (kMarch2lSerpentine in
- * k_spmv.hip). */
+ * k_spmv.hip).
+ * Pipelined body of the fused launches of variants 22 / 23 (every plane loaded through LDS one plane
+ * ahead; 104 KiB of LDS per workgroup; alpha and beta bitwise unchanged): by default on where the launch
+ * has at most one workgroup per CU anyway (two plane runs on planes of at least 1024 columns) and, where
+ * the variant is the automatic choice, the rank owns at least EIG_MARCH_PIPE_MIN_ROWS rows;
+ * bit 5 (32) = never (the A/B arm); bit 6 (64) = wherever the body can run (tests reach small grids);
+ * eig_mat_info.march_pipe tells which. */
 /* EIG_TUNE_HALO (distributed Lanczos steps): 0 = the interior planes run while the halo is in flight
  * and the boundary planes after it (two launches, the default); 1 = the exchange first, then ONE
  * launch over all owned rows (no second launch's fixed cost; the exchange is exposed).  The step's
@@ -301,6 +309,9 @@ enum { EIG_TUNE_MARCH_RUNS = 1, EIG_TUNE_BOX_SEGS = 2, EIG_TUNE_MARCH_PREFETCH =
  * 0 = automatic: the fused step on 3-D value images takes variant 22 on ranks of at least
  * EIG_MARCH_2L_MIN_ROWS owned rows, else 15.  Bitwise the same rows for every value. */
 #define EIG_MARCH_2L_MIN_ROWS 4194304
+/* Owned rows from which the fused launches of the automatically chosen variant 22 take the pipelined body
+ * (EIG_TUNE_CACHE bits 5 / 6; measured on 256^2 slabs: slower at 32 and 64 planes, faster from 128). */
+#define EIG_MARCH_PIPE_MIN_ROWS 8388608
 int eig_mat_tune(eig_mat_t mat, int key, int value);
 
 /* a13: A += shift*I on the diagonal of every diagonal block (eigensolver.hh:59-66). */
@@ -482,6 +493,9 @@ int eig_lanczos_destroy(eig_lanczos_t ws);
 /* Logical steps taken and kernel launches issued (fused: steps + repairs + forced final repairs;
  * two-kernel: = steps). */
 int eig_lanczos_info(eig_lanczos_t ws, int *steps, int *launches);
+/* Test / measurement helper: the (t, u) pairs the fused step's last launch wrote, interleaved, for the
+ * `rows` owned rows of a 1x1 matrix (2 * rows doubles; EIG_LANCZOS_FUSED workspaces only). */
+int eig_lanczos_pairs(eig_lanczos_t ws, double *pairs_host, int64_t rows);
 /* The recurrence the workspace runs (*variant: 0 two-kernel, EIG_LANCZOS_FUSED or
  * EIG_LANCZOS_PIPELINED, after EIG_LANCZOS_AUTO resolved it), its step kernel (name, at most
  * name_len bytes) and that kernel's algorithmic bytes per launch (as eig_lanczos_kernel_info). */

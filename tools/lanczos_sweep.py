@@ -136,6 +136,7 @@ def main():
         info = M.info
         ib = eigmi.image_bytes(M, "spmv") + (16 * n if op == "fused" else 0)  # bytes the image streams
         print(json.dumps({"variant": spec, "matrix": args.matrix, "march_variant": info.march_variant,
+                          "march_pipe": info.march_pipe,  # (%32 = never pipeline, the A/B arm; %64 = wherever it can)
                           "comm": args.comm,
                           "image_bytes": ib if op in ("mv", "fused") else None,
                           "image_frac": round(ib / (float(np.median(res[spec]["k_us"])) * 1e3) / 8000, 4)

@@ -8,6 +8,8 @@
 // `march_copy N values`: the value march's streams instead (k_vmarch; GB/s over 64 B per row).
 // `march_copy N values serpentine [runs] [rounds]`: the 2-line full-step probe with every second launch
 // marching down, against all launches marching up, each with nontemporal and plain pair stores.
+// `march_copy N values pipeline [runs] [rounds]`: the same probe with every loop load as an LDS-DMA issued one
+// plane ahead (k_vabl2p), against the plain probe; checks first that both write the same pairs bit for bit.
 // `march_copy N kuhn`: the P1 Kuhn march's streams (k_kmarch; GB/s over 96 B per row).
 // `march_copy N box`: the C5 Chebyshev step's streams as a plain copy (k_boxcopy; 1152 B per row).
 //   linear     grid-stride 16-B copy (the reference rate)
@@ -23,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include <algorithm>
 #include <string>
@@ -505,6 +508,199 @@ __global__ __launch_bounds__(kThreads, W) void k_vabl2(int n, int D, int nx, int
   }
 }
 
+// k_vabl2's step with every loop load as an LDS-DMA issued one plane ahead (the "pipeline" probe): per
+// wave two LDS buffers of kPipeRegions lane-linear 1-KiB regions (base + lane * 16 B), one region per load.
+// Iteration z issues plane z + 1's DMAs into the other buffer, waits with one counted vmcnt that retires
+// plane z's DMAs (the new ones and plane z - 1's two stores stay in flight), reads its operands back with
+// ds_read_b128 and does k_vabl2's arithmetic in k_vabl2's order.  The regions are wave-private: no barrier;
+// a buffer is refilled only after its reads returned (lgkmcnt(0) inside the read statement).  The 8-B
+// loads become 16-B DMAs of the pair that holds them.
+constexpr int kPipeRegions = 13;
+constexpr size_t kPipeLds = (size_t)kW * 2 * kPipeRegions * 64 * sizeof(dpair);
+template <unsigned AUX>
+__device__ __forceinline__ void glds16(const dpair *g, dpair *l)
+{
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
+                                   (__attribute__((address_space(3))) void *)l, 16, 0, AUX);
+}
+// four / five 16-B LDS reads at byte address a + k KiB and the wait for them, in one statement (the
+// compiler does not see an LDS-DMA's write, so it is not left to order or count these reads)
+__device__ __forceinline__ void lds_read4(unsigned a, dpair &r0, dpair &r1, dpair &r2, dpair &r3)
+{
+  asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\t"
+               "ds_read_b128 %3, %4 offset:3072\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
+               : "v"(a)
+               : "memory");
+}
+__device__ __forceinline__ void lds_read5(unsigned a, dpair &r0, dpair &r1, dpair &r2, dpair &r3, dpair &r4)
+{
+  asm volatile("ds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:1024\n\tds_read_b128 %2, %5 offset:2048\n\t"
+               "ds_read_b128 %3, %5 offset:3072\n\tds_read_b128 %4, %5 offset:4096\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4)
+               : "v"(a)
+               : "memory");
+}
+template <int W, bool DOWN = false>
+__global__ __launch_bounds__(kThreads, W) void k_vabl2p(int n, int D, int nx, int ncol, int nseg, int nplanes,
+                                                        const dpair *__restrict__ P, const dpair *__restrict__ V,
+                                                        dpair *__restrict__ Q, double *__restrict__ sums, double c)
+{
+  extern __shared__ dpair pipe_lds[];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ncol2 = ncol / 2, xc = nx / 64;
+  const int item = swz() * kW + wave;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  if (item < ncol2 * nseg)
+  {
+    const int col2 = item % ncol2, seg = item / ncol2;
+    const int z0 = seg * nplanes / nseg, z1 = (seg + 1) * nplanes / nseg;
+    const int lastrow = n - 1;
+    auto cl = [&](int g) { return g < 0 ? 0 : (g > lastrow ? lastrow : g); };
+    const int line0 = 2 * (col2 / xc);
+    constexpr int DIR = DOWN ? -1 : 1;
+    int w = line0 * nx + (col2 % xc) * 64 + lane + (DOWN ? z1 - 1 : z0) * D;
+    dpair cur0 = P[cl(w)], cur1 = P[cl(w + nx)];
+    dpair prev0 = P[cl(w - DIR * D)], prev1 = P[cl(w + nx - DIR * D)];
+    dpair av0 = dpair{0.0, 0.0}, av1 = dpair{0.0, 0.0};
+    if (DOWN)
+    {
+      av0 = __builtin_nontemporal_load(V + w);
+      av1 = __builtin_nontemporal_load(V + w + nx);
+    }
+    // make the ordinary loads land before the first DMA is issued (a use of them later would drain the DMAs)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(cur0), "+v"(cur1), "+v"(prev0), "+v"(prev1), "+v"(av0), "+v"(av1));
+    dpair *const wb = pipe_lds + wave * (2 * kPipeRegions * 64);
+    const unsigned rd0 = (unsigned)(size_t)(__attribute__((address_space(3))) dpair *)(wb + lane);  // LDS byte address
+    const bool edge = lane == 0 || lane == 63;
+    // regions: 0, 1 the next plane's pairs; 2, 3 the (+D, 0) values; 4, 5 the (+1, +nx) values; 6, 7 the
+    // gathered operands of lines y0 - 1, y0 + 2; 8 line y0 - 1's mirrored value; 9, 10 the x-edge operands
+    // (lanes 0 and 63); 11, 12 lane 0's mirrored -1 values
+    auto issue = [&](int wz, int b) {
+      dpair *L = wb + b * (kPipeRegions * 64);
+      glds16<0>(P + cl(wz + DIR * D), L);
+      glds16<0>(P + cl(wz + nx + DIR * D), L + 64);
+      glds16<2>(V + cl(DOWN ? wz - D : wz), L + 2 * 64);
+      glds16<2>(V + cl(DOWN ? wz + nx - D : wz + nx), L + 3 * 64);
+      glds16<0>(V + n + wz, L + 4 * 64);
+      glds16<0>(V + n + wz + nx, L + 5 * 64);
+      glds16<0>(P + cl(wz - nx), L + 6 * 64);
+      glds16<0>(P + cl(wz + 2 * nx), L + 7 * 64);
+      glds16<0>(V + n + cl(wz - nx), L + 8 * 64);
+      if (edge)
+      {
+        glds16<0>(P + cl(lane == 0 ? wz - 1 : wz + 1), L + 9 * 64);
+        glds16<0>(P + cl(lane == 0 ? wz + nx - 1 : wz + nx + 1), L + 10 * 64);
+      }
+      if (lane == 0)
+      {
+        glds16<0>(V + n + cl(wz - 1), L + 11 * 64);
+        glds16<0>(V + n + cl(wz + nx - 1), L + 12 * 64);
+      }
+    };
+    auto uk = [&](dpair p) { return p.x - c * p.y; };
+    issue(w, 0);
+    int b = 0;
+    for (int z = z0; z < z1; ++z, w += DIR * D, b ^= 1)
+    {
+      // in order on the counter: plane z's 13 DMAs, plane z - 1's 2 stores, plane z + 1's 13 DMAs
+      if (z + 1 < z1)
+      {
+        issue(w + DIR * D, b ^ 1);
+        if (z == z0)
+          asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
+        else
+          asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
+      }
+      else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned ra = rd0 + (unsigned)b * (unsigned)(kPipeRegions * 64 * sizeof(dpair));
+      dpair pd0, pd1, l0, l1, b0, b1, u, v, mn, e0, e1, me0, me1;
+      lds_read4(ra, pd0, pd1, l0, l1);
+      lds_read4(ra + 4 * 1024, b0, b1, u, v);
+      lds_read5(ra + 8 * 1024, mn, e0, e1, me0, me1);
+      const dpair a0 = DOWN ? dpair{av0.x, l0.x} : l0, a1 = DOWN ? dpair{av1.x, l1.x} : l1;
+      av0 = l0;
+      av1 = l1;
+      const double mnx0 = mn.y;
+      const double m1e0 = lane == 0 ? me0.x : 0.0, m1e1 = lane == 0 ? me1.x : 0.0;
+      const double vc0 = uk(cur0), vc1 = uk(cur1);
+      auto row = [&](dpair a, dpair bb, dpair prev, double mnx, double vn, double m1e, dpair e, double vc, double vq,
+                     dpair pd, dpair cur) {
+        const double vl = __shfl_up(vc, 1, 64), vr = __shfl_down(vc, 1, 64);
+        const double am1 = lane == 0 ? m1e : __shfl_up(bb.x, 1, 64);
+        double acc = 0.0;
+        acc += bb.y * uk(prev);
+        acc += mnx * vn;
+        acc += am1 * (lane == 0 ? uk(e) : vl);
+        acc += a.x * vc;
+        acc += bb.x * (lane == 63 ? uk(e) : vr);
+        acc += bb.y * vq;
+        acc += a.x * uk(pd);
+        const double t = (acc - 0.5 * vc) * 0.25 - 0.125 * cur.y;
+        s0 += t * vc;
+        s1 += t * t;
+        s2 += vc * vc;
+        return dpair{t, vc};
+      };
+      const dpair o0 = row(a0, b0, prev0, mnx0, uk(u), m1e0, e0, vc0, vc1, pd0, cur0);
+      const dpair o1 = row(a1, b1, prev1, b0.y, vc0, m1e1, e1, vc1, uk(v), pd1, cur1);
+      __builtin_nontemporal_store(o0, Q + w);
+      __builtin_nontemporal_store(o1, Q + w + nx);
+      prev0 = cur0;
+      prev1 = cur1;
+      cur0 = pd0;
+      cur1 = pd1;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1)
+  {
+    s0 += __shfl_down(s0, off, 64);
+    s1 += __shfl_down(s1, off, 64);
+    s2 += __shfl_down(s2, off, 64);
+  }
+  __shared__ double ws[kW][3];
+  __shared__ int last;
+  if (lane == 0)
+  {
+    ws[wave][0] = s0;
+    ws[wave][1] = s1;
+    ws[wave][2] = s2;
+  }
+  __syncthreads();
+  double *part = sums + 64;
+  unsigned *ticket = reinterpret_cast<unsigned *>(sums);
+  if (threadIdx.x < 3)
+  {
+    double t = 0.0;
+    for (int q = 0; q < kW; ++q) t += ws[q][threadIdx.x];
+    __hip_atomic_store(reinterpret_cast<unsigned long long *>(part + 3 * blockIdx.x + threadIdx.x),
+                       (unsigned long long)__double_as_longlong(t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0)
+    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  __syncthreads();
+  if (last)
+  {
+    double a0 = 0.0;
+    for (unsigned bk = threadIdx.x; bk < 3 * gridDim.x; bk += kThreads)
+      a0 += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long *>(part + bk),
+                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    for (int off = 32; off > 0; off >>= 1) a0 += __shfl_down(a0, off, 64);
+    if (lane == 0) atomicAdd(sums + 8, a0);
+    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// fill of the pipeline probe's check: values that make every product and sum of the step finite and distinct
+__global__ void k_fill(size_t m, dpair *p, double s)
+{
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < m; i += (size_t)gridDim.x * blockDim.x)
+    p[i] = dpair{s * (double)((i * 2654435761u) & 1023) + 0.25, s * (double)((i * 40503u) & 511) - 0.125};
+}
+
 // The same with LN grid lines per wave (LN = 2 reproduces k_vabl2's loads): lines y0 .. y0 + LN - 1,
 // only line y0 - 1's operand / mirrored value and line y0 + LN's operand gathered
 template <int LN, int W>
@@ -760,6 +956,104 @@ int main(int argc, char **argv)
                 k_vabl2<5, true, true><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
               else
                 k_vabl2<5, false, true><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
+            }
+            else
+            {
+              if (down)
+                k_vabl2<5, true, false><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
+              else
+                k_vabl2<5, false, false><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
+            }
+          });
+          us[arm].push_back(t);
+          std::printf("{\"pattern\": \"%s\", \"N\": %d, \"runs\": %d, \"round\": %d, \"us\": %.2f, \"GBs\": %.1f}\n",
+                      names[arm], N, nseg, r, t, 4.0 * n * sizeof(dpair) / t * 1e-3);
+          std::fflush(stdout);
+        }
+      for (int arm = 0; arm < kArms; ++arm)
+      {
+        std::sort(us[arm].begin(), us[arm].end());
+        std::printf("{\"pattern\": \"%s\", \"N\": %d, \"runs\": %d, \"rounds\": %d, \"us_med\": %.2f, "
+                    "\"us_min\": %.2f, \"us_max\": %.2f, \"spread_us\": %.2f}\n",
+                    names[arm], N, nseg, rounds, us[arm][us[arm].size() / 2], us[arm].front(), us[arm].back(),
+                    us[arm].back() - us[arm].front());
+      }
+      CK(hipGetLastError());
+      CK(hipFree(sums));
+      CK(hipFree(V));
+      CK(hipFree(P));
+      CK(hipFree(Q));
+      return 0;
+    }
+    if (argc > 3 && std::string(argv[3]) == "pipeline")
+    {
+      // The LDS-DMA pipeline (k_vabl2p) against the 2-line full-step probe (k_vabl2<5>) at `runs` plane runs,
+      // ping-pong, every second launch marching down.  First a check on non-zero data (one upward and one
+      // downward launch of each kernel must write the same pairs bit for bit), then the timed arms on zeroed
+      // data as in the other probes, alternating round by round; read the ratio of the two updown arms.
+      double *sums;
+      const int nseg = argc > 4 ? std::atoi(argv[4]) : 2, rounds = argc > 5 ? std::atoi(argv[5]) : 7;
+      const int G2 = ((ncol / 2) * nseg + kW - 1) / kW;
+      CK(hipMalloc(&sums, (size_t)(3 * G2 + 64) * sizeof(double)));
+      CK(hipMemset(sums, 0, (size_t)(3 * G2 + 64) * sizeof(double)));
+      CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_vabl2p<5, false>),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLds));
+      CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_vabl2p<5, true>),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPipeLds));
+      {
+        dpair *Q2;
+        CK(hipMalloc(&Q2, (size_t)n * sizeof(dpair)));
+        k_fill<<<2048, 256>>>((size_t)n, P, 1.0 / 1024);
+        k_fill<<<2048, 256>>>((size_t)2 * n, V, 1.0 / 4096);
+        std::vector<char> ha((size_t)n * sizeof(dpair)), hb((size_t)n * sizeof(dpair));
+        for (int down = 0; down < 2; ++down)
+        {
+          CK(hipMemset(Q, 0xff, (size_t)n * sizeof(dpair)));
+          CK(hipMemset(Q2, 0x7f, (size_t)n * sizeof(dpair)));
+          if (down)
+          {
+            k_vabl2<5, true, false><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, P, V, Q, sums, 0.5);
+            k_vabl2p<5, true><<<G2, kThreads, kPipeLds>>>(n, D, nx, ncol, nseg, NZ, P, V, Q2, sums, 0.5);
+          }
+          else
+          {
+            k_vabl2<5, false, false><<<G2, kThreads>>>(n, D, nx, ncol, nseg, NZ, P, V, Q, sums, 0.5);
+            k_vabl2p<5, false><<<G2, kThreads, kPipeLds>>>(n, D, nx, ncol, nseg, NZ, P, V, Q2, sums, 0.5);
+          }
+          CK(hipGetLastError());
+          CK(hipMemcpy(ha.data(), Q, ha.size(), hipMemcpyDeviceToHost));
+          CK(hipMemcpy(hb.data(), Q2, hb.size(), hipMemcpyDeviceToHost));
+          size_t bad = 0;
+          for (size_t i = 0; i < ha.size(); i += sizeof(dpair))
+            bad += std::memcmp(ha.data() + i, hb.data() + i, sizeof(dpair)) != 0;
+          std::printf("{\"pattern\": \"pipe_check_%s\", \"N\": %d, \"runs\": %d, \"rows\": %d, \"rows_differing\": %zu}\n",
+                      down ? "down" : "up", N, nseg, n, bad);
+          std::fflush(stdout);
+          if (bad) return 3;
+        }
+        CK(hipFree(Q2));
+        CK(hipMemset(P, 0, (size_t)n * sizeof(dpair)));
+        CK(hipMemset(Q, 0, (size_t)n * sizeof(dpair)));
+        CK(hipMemset(V, 0, (size_t)2 * n * sizeof(dpair)));
+        CK(hipMemset(sums, 0, (size_t)(3 * G2 + 64) * sizeof(double)));
+      }
+      constexpr int kArms = 6;
+      const char *names[kArms] = {"pipe_off_updown", "pipe_on_updown", "pipe_off_upup",
+                                  "pipe_on_upup",    "pipe_off_downdown", "pipe_on_downdown"};
+      std::vector<double> us[kArms];
+      for (int r = 0; r < rounds; ++r)
+        for (int arm = 0; arm < kArms; ++arm)
+        {
+          const bool pipe = arm & 1;
+          rep = 0;  // every arm starts on P
+          const double t = time([&] {
+            const bool down = arm >= 4 || (arm < 2 && (rep & 1));
+            if (pipe)
+            {
+              if (down)
+                k_vabl2p<5, true><<<G2, kThreads, kPipeLds>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
+              else
+                k_vabl2p<5, false><<<G2, kThreads, kPipeLds>>>(n, D, nx, ncol, nseg, NZ, src(), V, dst(), sums, 0.5);
             }
             else
             {
