@@ -9,6 +9,9 @@
 // The reference reaches the same pencil through GeneralizedInverse (UMFPACK LU + subspace
 // iteration, eigensolver.hh:204-351) or ARPACK shift-invert (arpack_geneo_wrapper.hh:581-658);
 // both need a sparse factorisation, which does not exist at C5's size (hard part 4).
+// Square blocks b = 2..4 (one rank): every vector has n = nb_rows * b scalar rows, the products are
+// k_spmm_blk_mv8, the Chebyshev step k_spmm_blk_mv8_cheb (k_mv8.hip) with point Jacobi on the scalar
+// diagonal of the diagonal blocks (k_diag_inv_blk); panels, CholQR2 and k_cheb_init see scalar rows only.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -82,13 +85,16 @@ namespace eigmi {
 double *cheb_solve(eig_mat_s &M, i64 m, int degree, double lmin, double lmax, const double *Bv, const double *dinv,
                    double *Xa, double *Xb, double *Xc, hipStream_t s)
 {
-  const i64 n = M.nb_rows, ld = M.window, own = M.own_offset;
+  // scalar rows; ld and own are scalar units already.  Square blocks 2..4 (one rank) take the in-place
+  // two-buffer branch below: the box kernels are 1x1 images
+  const bool blocked = M.br > 1 || M.bc > 1;
+  const i64 n = M.nb_rows * M.br, ld = M.window, own = M.own_offset;
   const double gamma = 2.0 / (lmin + lmax), mu = (lmax - lmin) / (lmax + lmin);
   double omega = 1.0 / (1.0 - 0.5 * mu * mu);  // omega_1
   // Row-class image (one rank): x_1 = gamma D^-1 b is never stored -- the first step forms it while
   // b's planes enter the LDS ring (x_2 straight from b), the second forms x_{k-1} = x_1 from the
   // row's b.  Same arithmetic as the k_cheb_init + box-step chain below.
-  if (degree >= 2 && Xc && !M.ctx->distributed() && launch_box_cheb_first(M, m, Bv, omega, gamma, Xa, s))
+  if (degree >= 2 && Xc && !blocked && !M.ctx->distributed() && launch_box_cheb_first(M, m, Bv, omega, gamma, Xa, s))
   {
     if (degree == 2) return Xa;
     omega = 1.0 / (1.0 - 0.25 * mu * mu * omega);
@@ -111,7 +117,7 @@ double *cheb_solve(eig_mat_s &M, i64 m, int degree, double lmin, double lmax, co
   }
   launch_cheb_init(n, ld, own, m, Bv, dinv, gamma, Xa, s);
   if (degree <= 1) return Xa;
-  const bool oop = Xc && m % 32 == 0 && box_prepare(M);
+  const bool oop = Xc && !blocked && m % 32 == 0 && box_prepare(M);
   // x_0 = 0: the box kernel (a third output buffer) takes it as "not read"; the in-place kernels
   // read a cleared buffer
   if (!oop) EIG_HIP(hipMemsetAsync(Xb, 0, (size_t)ld * m * sizeof(double), s));
@@ -163,7 +169,7 @@ void mcholqr2(eig_blanczos_s &w, double *Z, double *Vdst, std::vector<double> &R
   int *flag = reinterpret_cast<int *>(Rt + (size_t)b * b);
   EIG_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
   halo_mv(M, Z, b, s);
-  launch_sell_mv8(M, b, Z, dptr(w.MZ), s);
+  launch_spmm_mv8(M, b, Z, dptr(w.MZ), s);
   launch_panel_gram(ctx, n, ld, b, b, Z + own * 8, dptr(w.MZ) + own * 8, Gd, s);
   allreduce_sum(ctx, Gd, (i64)b * b, s);
   launch_chol_small(b, 0, Gd, Rd, Sd, Rt, flag, s);  // Sd = R0^-1, Rt = R0
@@ -198,7 +204,7 @@ void mcholqr2(eig_blanczos_s &w, double *Z, double *Vdst, std::vector<double> &R
     else
     {
       halo_mv(M, Z, b, s);
-      launch_sell_mv8(M, b, Z, dptr(w.MZ), s);
+      launch_spmm_mv8(M, b, Z, dptr(w.MZ), s);
     }
     launch_panel_gram(ctx, n, ld, b, b, Z + own * 8, dptr(w.MZ) + own * 8, Gd, s);
   }
@@ -217,8 +223,12 @@ void mcholqr2(eig_blanczos_s &w, double *Z, double *Vdst, std::vector<double> &R
 void check_pair(const eig_mat_s *K, const eig_mat_s *M)
 {
   EIG_CHECK(K && M && K->ctx == M->ctx, EIG_ERR_ARG, "block Lanczos: K and M must share a context");
-  EIG_CHECK(K->br == 1 && K->bc == 1 && M->br == 1 && M->bc == 1, EIG_ERR_BLOCKSIZE,
-            "block Lanczos: FieldMatrix<double,1,1> only");
+  // 1x1 blocks (any context), or equal square blocks 2..4 on one rank (the blocked product and
+  // Chebyshev step have no halo split)
+  EIG_CHECK(K->br == K->bc && M->br == M->bc && K->br == M->br && K->br >= 1 && K->br <= 4, EIG_ERR_BLOCKSIZE,
+            "block Lanczos: K and M need the same square blocks, FieldMatrix<double,b,b> with b = 1..4");
+  EIG_CHECK(K->br == 1 || !K->ctx->distributed(), EIG_ERR_BLOCKSIZE,
+            "block Lanczos: blocked matrices on one rank only");
   EIG_CHECK(K->nb_rows == M->nb_rows && K->row_begin == M->row_begin && K->window == M->window &&
                 K->own_offset == M->own_offset && K->nb_rows_global == M->nb_rows_global,
             EIG_ERR_SHAPE, "block Lanczos: K and M must have the same rows and column window");
@@ -237,7 +247,7 @@ void blanczos_create(eig_mat_t K, eig_mat_t M, eig_mat_t Ks, double sigma, int b
               EIG_ERR_ARG, "eig_blanczos_create: block in {8,16,24,32}, max_steps >= 1, degree >= 1, 0 < lmin < lmax");
     check_pair(K, M);
     if (Ks) check_pair(Ks, M);
-    EIG_CHECK((i64)(max_steps + 1) * block <= K->nb_rows_global, EIG_ERR_SHAPE,
+    EIG_CHECK((i64)(max_steps + 1) * block <= K->nb_rows_global * K->br, EIG_ERR_SHAPE,
               "eig_blanczos_create: (max_steps + 1) * block exceeds the matrix size");
     eig_ctx_t ctx = K->ctx;
     EIG_HIP(hipSetDevice(ctx->device));
@@ -259,7 +269,7 @@ void blanczos_create(eig_mat_t K, eig_mat_t M, eig_mat_t Ks, double sigma, int b
       w->lmax = lmax;
       w->ld = K->window;
       w->own = K->own_offset;
-      w->n = K->nb_rows;
+      w->n = K->nb_rows * K->br;  // scalar rows
       const size_t blk = (size_t)w->ld * block * sizeof(double);
       w->V = new DevBuf(blk * (max_steps + 1));
       w->W = new DevBuf(blk);
@@ -274,9 +284,9 @@ void blanczos_create(eig_mat_t K, eig_mat_t M, eig_mat_t Ks, double sigma, int b
       for (DevBuf *d : {w->W, w->Xa, w->Xb, w->MZ}) EIG_HIP(hipMemsetAsync(d->d(), 0, d->bytes(), s));
       launch_diag_inv(Ks ? *Ks : *M, w->dinv->d(), s);
       // start block: mt19937(seed) + normal(0,1) in MultiVector fill order (block, row, col) over
-      // the GLOBAL rows (eigensolver.hh:49-55), this rank keeps its own rows
+      // the GLOBAL scalar rows (eigensolver.hh:49-55), this rank keeps its own rows
       {
-        const i64 ng = K->nb_rows_global, rb = K->row_begin, n = w->n;
+        const i64 ng = K->nb_rows_global * K->br, rb = K->row_begin * K->br, n = w->n;
         std::vector<double> h((size_t)w->ld * block, 0.0);
         std::mt19937 urbg{seed};
         std::normal_distribution<double> gen{0.0, 1.0};
@@ -370,7 +380,7 @@ extern "C" int eig_blanczos_step(eig_blanczos_t w, int steps, eig_blanczos_timin
       {
         // W = K V_j;  Z = M^-1 W;  A_j = V_j^T W is block j of the first CGS pass's V^T W below
         halo_mv(*w->K, Vj, b, s);
-        launch_sell_mv8(*w->K, b, Vj, w->W->d(), s);
+        launch_spmm_mv8(*w->K, b, Vj, w->W->d(), s);
         EIG_HIP(hipEventRecord(e[1], s));
         Z = cheb_solve(*w->M, b, w->degree, w->lmin, w->lmax, w->W->d(), w->dinv->d(), w->Xa->d(), w->Xb->d(),
                        w->Xc->d(), s);
@@ -380,7 +390,7 @@ extern "C" int eig_blanczos_step(eig_blanczos_t w, int steps, eig_blanczos_timin
       {
         // W = M V_j;  Z = Ks^-1 W = OP V_j;  A_j = V_j^T M Z = W^T Z
         halo_mv(*w->M, Vj, b, s);
-        launch_sell_mv8(*w->M, b, Vj, w->W->d(), s);
+        launch_spmm_mv8(*w->M, b, Vj, w->W->d(), s);
         EIG_HIP(hipEventRecord(e[1], s));
         if (w->mg)
         {
@@ -406,7 +416,7 @@ extern "C" int eig_blanczos_step(eig_blanczos_t w, int steps, eig_blanczos_timin
         else
         {
           halo_mv(*w->M, Z, b, s);
-          launch_sell_mv8(*w->M, b, Z, w->MZ->d(), s);
+          launch_spmm_mv8(*w->M, b, Z, w->MZ->d(), s);
         }
         launch_panel_gram(ctx, n, ld, m1, b, w->V->d() + own * 8, MZ + own * 8, Cd, s);
         allreduce_sum(ctx, Cd, m1 * b, s);
@@ -448,7 +458,7 @@ extern "C" int eig_blanczos_step(eig_blanczos_t w, int steps, eig_blanczos_timin
         timing->total_ms = tt;
       }
       timing->steps = steps;
-      timing->cheb_launches = (int64_t)steps * std::max(0, w->degree - 1) * sell_mv8_launches(b);
+      timing->cheb_launches = (int64_t)steps * std::max(0, w->degree - 1) * cheb_step_launches(solve_mat(*w), b);
       timing->cholqr_recomputed = w->cholqr_recomputed;
     }
   });
@@ -541,8 +551,8 @@ extern "C" int eig_blanczos_ritz(eig_blanczos_t w, int nev, int which, double *e
       if (resid_host)
       {
         halo_mv(*w->K, Y, m2, s);
-        launch_sell_mv8(*w->K, m2, Y, w->W->d(), s);
-        launch_sell_mv8(*w->M, m2, Y, w->MZ->d(), s);
+        launch_spmm_mv8(*w->K, m2, Y, w->W->d(), s);
+        launch_spmm_mv8(*w->M, m2, Y, w->MZ->d(), s);
         hk.resize(hy.size());
         hm.resize(hy.size());
         EIG_HIP(hipMemcpyAsync(hk.data(), w->W->d(), hk.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -596,14 +606,16 @@ extern "C" int eig_mass_solve_mv8(eig_mat_t M, int64_t m, int degree, double lmi
   return guard(M ? M->ctx : nullptr, [&] {
     EIG_CHECK(M && B && X && m > 0 && m % 8 == 0 && degree >= 1 && lmin > 0.0 && lmax > lmin, EIG_ERR_ARG,
               "eig_mass_solve_mv8: bad argument");
-    EIG_CHECK(M->br == 1 && M->bc == 1 && M->nb_rows_global == M->nb_cols, EIG_ERR_BLOCKSIZE,
-              "eig_mass_solve_mv8: square FieldMatrix<double,1,1> only");
+    EIG_CHECK(M->br == M->bc && M->br >= 1 && M->br <= 4 && M->nb_rows_global == M->nb_cols &&
+                  (M->br == 1 || !M->ctx->distributed()),
+              EIG_ERR_BLOCKSIZE,
+              "eig_mass_solve_mv8: square matrix of FieldMatrix<double,b,b>, b = 1..4 (b > 1: one rank)");
     EIG_CHECK(X != B, EIG_ERR_ARG, "eig_mass_solve_mv8: X must not alias B (B is read by every step)");
     eig_ctx_t ctx = M->ctx;
     EIG_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t bytes = (size_t)M->window * m * sizeof(double);
-    DevBuf dinv((size_t)std::max<i64>(M->nb_rows, 1) * sizeof(double)), Xb(bytes), Xc(bytes);
+    DevBuf dinv((size_t)std::max<i64>(M->nb_rows * M->br, 1) * sizeof(double)), Xb(bytes), Xc(bytes);
     launch_diag_inv(*M, dinv.d(), s);
     EIG_HIP(hipMemsetAsync(X, 0, bytes, s));
     double *res = cheb_solve(*M, m, degree, lmin, lmax, B, dinv.d(), X, Xb.d(), Xc.d(), s);

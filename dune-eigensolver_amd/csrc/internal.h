@@ -540,6 +540,15 @@ void launch_sell_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, hipS
 int sell_mv8_launches(i64 m);  // kernel launches per launch_sell_mv8 / launch_cheb_step call
 void launch_cheb_step(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *B, const double *dinv,
                       double omega, double gamma, hipStream_t s);
+// kernel launches per launch_cheb_step call on M: sell_mv8_launches(m) for 1x1 blocks, one for the
+// blocked kernel
+int cheb_step_launches(const eig_mat_s &M, i64 m);
+// The same step on square blocks 2..4 (k_mv8.hip k_spmm_blk_mv8_cheb; one rank, R = 1, square matrix):
+// launch_cheb_step dispatches here.  Vectors have nb_rows * br scalar rows, dinv is the scalar diagonal's.
+void launch_cheb_step_blk(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *B,
+                          const double *dinv, double omega, double gamma, hipStream_t s);
+// dinv[i] = 1 / a_ii over the owned scalar rows: 1x1 blocks, or (one rank) the scalar diagonal of the
+// diagonal blocks of square blocks 2..4
 void launch_diag_inv(const eig_mat_s &A, double *dinv, hipStream_t s);
 void launch_cheb_init(i64 n, i64 ld, i64 own, i64 m, const double *B, const double *dinv, double gamma, double *X,
                       hipStream_t s);

@@ -6,6 +6,7 @@
 //                     epilogue kStore (plain SpMM, a2) or kCheb (one Chebyshev-Jacobi step of the
 //                     mass solve, fused into the SpMM)
 //   k_diag_inv        dinv[r] = 1 / a_rr
+//   k_diag_inv_blk    the same from b x b blocks: the scalar diagonal of the diagonal blocks
 //   k_cheb_init       X = gamma * dinv o B
 //   k_panel_gram_*    G = Q1^T Q2 for tall-skinny panels on MFMA (v_mfma_f64_16x16x4f64), two
 //                     deterministic stages (per-workgroup partials, then a fixed-order sum)
@@ -441,9 +442,22 @@ void launch_resid_mv8(const eig_mat_s &A, i64 m, const double *X, const double *
   sell_mv8<kResid>(A, m, X, R, B, nullptr, 0.0, 0.0, s);
 }
 
+int cheb_step_launches(const eig_mat_s &M, i64 m)
+{
+  // square blocks: one k_spmm_blk_mv8_cheb launch takes every column block (grid.y)
+  if (M.br == M.bc && M.br > 1) return m >= 8 ? 1 : 0;
+  return sell_mv8_launches(m);
+}
+
 void launch_cheb_step(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *B, const double *dinv,
                       double omega, double gamma, hipStream_t s)
 {
+  if (M.br == M.bc && M.br > 1)
+  {
+    // square blocks 2..4: the epilogue on the blocked product (k_mv8.hip), dinv the scalar diagonal's
+    launch_cheb_step_blk(M, m, Xk, Xold, B, dinv, omega, gamma, s);
+    return;
+  }
   // symmetric band image with a marchable band (the P1 mass matrix of config C5): k_spmm8_marchg
   if (launch_box_cheb(M, m, Xk, Xold, B, dinv, omega, gamma, s)) return;
   if (launch_cheb_march(M, m, Xk, Xold, B, dinv, omega, gamma, s)) return;
@@ -468,8 +482,38 @@ __global__ void k_diag_inv(i64 nrows, int C, const i64 *__restrict__ slice_ptr, 
   }
 }
 
+// The same from the blocked SELL-64 image of b x b blocks (one rank): dinv[I b + r] = 1 / A_II[r][r],
+// the scalar diagonal of the diagonal block of block row I (block column `bown + I`); as above the
+// last matching stored block wins and a row without one gives 1 / 0.
+__global__ void k_diag_inv_blk(i64 nbrows, int b, const i64 *__restrict__ slice_ptr, const double *__restrict__ val,
+                               const i32 *__restrict__ col, i64 bown, double *__restrict__ dinv)
+{
+  const i64 n = nbrows * b;
+  const int bb = b * b;
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x)
+  {
+    const i64 I = i / b;
+    const int r = (int)(i - I * b);
+    const i64 s = I >> 6, l = I & 63;
+    const i64 base = slice_ptr[s];
+    const i64 w = (slice_ptr[s + 1] - base) >> 6;
+    double d = 0.0;
+    for (i64 k = 0; k < w; ++k)
+      if (col[base + k * 64 + l] == bown + I) d = val[(base + k * 64) * bb + (i64)(r * b + r) * 64 + l];
+    dinv[i] = 1.0 / d;
+  }
+}
+
 void launch_diag_inv(const eig_mat_s &A, double *dinv, hipStream_t s)
 {
+  if (A.br == A.bc && A.br >= 2 && A.br <= 4)
+  {
+    EIG_CHECK(!A.ctx->distributed() && A.R == 1, EIG_ERR_ARG, "diagonal extraction on blocks: single rank only");
+    hipLaunchKernelGGL(k_diag_inv_blk, dim3(grid_cap(A.nb_rows * A.br, 256, kStreamBlocks)), dim3(256), 0, s,
+                       A.nb_rows, A.br, A.slice_ptr, A.val, A.col, A.own_offset / A.br, dinv);
+    EIG_HIP(hipGetLastError());
+    return;
+  }
   EIG_CHECK(A.br == 1 && A.bc == 1, EIG_ERR_BLOCKSIZE, "diagonal extraction: 1x1 blocks only");
   hipLaunchKernelGGL(k_diag_inv, dim3(grid_cap(A.nb_rows, 256, kStreamBlocks)), dim3(256), 0, s, A.nb_rows,
                      (int)(64 * A.R), A.slice_ptr, A.val, A.col, A.own_offset, dinv);

@@ -15,6 +15,7 @@
 namespace eigmi {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
+typedef double dv2 __attribute__((ext_vector_type(2)));
 
 static inline int grid_for(i64 work, i64 per_block, int cap)
 {
@@ -90,71 +91,92 @@ __global__ __launch_bounds__(256) void k_spmm_mv8(i64 nrows, i64 nslices, const 
 // c = 0..B-1: s += a[r][c] * x[col*B + c] (products and sums rounded separately) -- the order of
 // k_spmv_blk, and of the 1x1 product on the matrix's scalar expansion, so the result is bitwise both.
 // ---------------------------------------------------------------------------------------------
+// The slices workgroup blockIdx.x walks: s0, s0 + step, ... < s1.  xcd_map (gridDim.x a multiple of
+// 8): the slices are cut into 8 contiguous shares and the workgroups with blockIdx.x % 8 == x -- dealt
+// to XCD x (round-robin dispatch: a speed assumption only, as k_sell_mv8q's) -- walk share x, so the
+// Qin rows an XCD's resident workgroups gather are one neighbourhood of the matrix, not the whole
+// front of the grid, and stay in its own L2.  Otherwise the plain grid stride.
+struct BlkSliceWalk {
+  i64 s0, s1, step;
+};
+__device__ __forceinline__ BlkSliceWalk blk_slice_walk(i64 nslices, int xcd_map)
+{
+  const i64 share = xcd_map ? (nslices + 7) / 8 : nslices;
+  BlkSliceWalk w;
+  w.s0 = xcd_map ? (blockIdx.x & 7) * share + (blockIdx.x >> 3) : blockIdx.x;
+  w.s1 = xcd_map ? min(nslices, ((blockIdx.x & 7) + 1) * share) : nslices;
+  w.step = xcd_map ? gridDim.x >> 3 : gridDim.x;
+  return w;
+}
+
+// acc[q][r] = column pair cp of (A Qin)(slice s, slice row ri, component r) for the column blocks
+// b0 + q < nblk_total: the row sums of the blocked product in the order stated above.  Padding entries
+// (col < 0) gather nothing.
+template <int B, int MB>
+__device__ __forceinline__ void spmm_blk_row(const i64 *__restrict__ slice_ptr, const double *__restrict__ val,
+                                             const i32 *__restrict__ col, const double *__restrict__ Qin, i64 n,
+                                             int nblk_total, int b0, i64 s, int ri, int cp, double2 (&acc)[MB][B])
+{
+  constexpr int BB = B * B;
+  const i64 base = slice_ptr[s];
+  const int width = (int)((slice_ptr[s + 1] - base) >> 6);
+#pragma unroll
+  for (int q = 0; q < MB; ++q)
+#pragma unroll
+    for (int r = 0; r < B; ++r) acc[q][r] = make_double2(0.0, 0.0);
+  i32 c = width > 0 ? __builtin_nontemporal_load(col + base + ri) : -1;
+  for (int k = 0; k < width; ++k)
+  {
+    const i32 cn = k + 1 < width ? __builtin_nontemporal_load(col + base + (i64)(k + 1) * 64 + ri) : -1;
+    if (c >= 0)
+    {
+      const double *vb = val + (base + (i64)k * 64) * BB + ri;
+      double a[BB];
+#pragma unroll
+      for (int t = 0; t < BB; ++t) a[t] = __builtin_nontemporal_load(vb + t * 64);
+#pragma unroll
+      for (int q = 0; q < MB; ++q)
+      {
+        if (b0 + q < nblk_total)
+        {
+          const double2 *xr = reinterpret_cast<const double2 *>(Qin + ((i64)(b0 + q) * n + (i64)c * B) * 8) + cp;
+          double2 xv[B];
+#pragma unroll
+          for (int cc = 0; cc < B; ++cc) xv[cc] = xr[cc * 4];
+#pragma unroll
+          for (int r = 0; r < B; ++r)
+          {
+            double2 sacc = acc[q][r];
+#pragma unroll
+            for (int cc = 0; cc < B; ++cc)
+            {
+              sacc.x += a[r * B + cc] * xv[cc].x;
+              sacc.y += a[r * B + cc] * xv[cc].y;
+            }
+            acc[q][r] = sacc;
+          }
+        }
+      }
+    }
+    c = cn;
+  }
+}
+
 template <int B, int MB>
 __global__ __launch_bounds__(256) void k_spmm_blk_mv8(i64 nbrows, i64 nslices, const i64 *__restrict__ slice_ptr,
                                                       const double *__restrict__ val, const i32 *__restrict__ col,
                                                       const double *__restrict__ Qin, double *__restrict__ Qout, i64 n,
                                                       int nblk_total, int xcd_map)
 {
-  constexpr int BB = B * B;
   const int wave = threadIdx.x >> 6, L = threadIdx.x & 63;
   const int cp = L & 3;
   const int ri = wave * 16 + (L >> 2);
   const int b0 = blockIdx.y * MB;
-  // slice schedule.  xcd_map (gridDim.x a multiple of 8): the slices are cut into 8 contiguous
-  // shares and the workgroups with blockIdx.x % 8 == x -- dealt to XCD x (round-robin dispatch: a
-  // speed assumption only, as k_sell_mv8q's) -- walk share x, so the Qin rows an XCD's resident
-  // workgroups gather are one neighbourhood of the matrix, not the whole front of the grid, and stay
-  // in its own L2.  Otherwise the plain grid stride.
-  const i64 share = xcd_map ? (nslices + 7) / 8 : nslices;
-  const i64 s0 = xcd_map ? (blockIdx.x & 7) * share + (blockIdx.x >> 3) : blockIdx.x;
-  const i64 s1 = xcd_map ? min(nslices, ((blockIdx.x & 7) + 1) * share) : nslices;
-  const i64 step = xcd_map ? gridDim.x >> 3 : gridDim.x;
-  for (i64 s = s0; s < s1; s += step)
+  const BlkSliceWalk w = blk_slice_walk(nslices, xcd_map);
+  for (i64 s = w.s0; s < w.s1; s += w.step)
   {
-    const i64 base = slice_ptr[s];
-    const int width = (int)((slice_ptr[s + 1] - base) >> 6);
     double2 acc[MB][B];
-#pragma unroll
-    for (int q = 0; q < MB; ++q)
-#pragma unroll
-      for (int r = 0; r < B; ++r) acc[q][r] = make_double2(0.0, 0.0);
-    i32 c = width > 0 ? __builtin_nontemporal_load(col + base + ri) : -1;
-    for (int k = 0; k < width; ++k)
-    {
-      const i32 cn = k + 1 < width ? __builtin_nontemporal_load(col + base + (i64)(k + 1) * 64 + ri) : -1;
-      if (c >= 0)
-      {
-        const double *vb = val + (base + (i64)k * 64) * BB + ri;
-        double a[BB];
-#pragma unroll
-        for (int t = 0; t < BB; ++t) a[t] = __builtin_nontemporal_load(vb + t * 64);
-#pragma unroll
-        for (int q = 0; q < MB; ++q)
-        {
-          if (b0 + q < nblk_total)
-          {
-            const double2 *xr = reinterpret_cast<const double2 *>(Qin + ((i64)(b0 + q) * n + (i64)c * B) * 8) + cp;
-            double2 xv[B];
-#pragma unroll
-            for (int cc = 0; cc < B; ++cc) xv[cc] = xr[cc * 4];
-#pragma unroll
-            for (int r = 0; r < B; ++r)
-            {
-              double2 sacc = acc[q][r];
-#pragma unroll
-              for (int cc = 0; cc < B; ++cc)
-              {
-                sacc.x += a[r * B + cc] * xv[cc].x;
-                sacc.y += a[r * B + cc] * xv[cc].y;
-              }
-              acc[q][r] = sacc;
-            }
-          }
-        }
-      }
-      c = cn;
-    }
+    spmm_blk_row<B, MB>(slice_ptr, val, col, Qin, n, nblk_total, b0, s, ri, cp, acc);
     const i64 row = s * 64 + ri;
     if (row < nbrows)
     {
@@ -170,6 +192,63 @@ __global__ __launch_bounds__(256) void k_spmm_blk_mv8(i64 nbrows, i64 nslices, c
   }
 }
 
+// One Chebyshev-Jacobi step of the mass solve fused into the blocked product (k_sell_mv8q<kCheb>'s
+// epilogue, k_block.hip, on the blocked image): the same image, lane mapping, slice schedule and row
+// sums as k_spmm_blk_mv8; then per scalar row I*B + r and column pair, with acc = (M x_k)_row,
+//     x_{k+1} = omega (x_k + (gamma dinv[row]) (b - acc) - x_{k-1}) + x_{k-1}
+// written in place over x_{k-1} (Xold: each lane reads its own rows before it stores them); x_k is
+// the gathered input Xk, never Xold.  dinv is the inverse SCALAR diagonal (k_diag_inv_blk).  dinv, b
+// and x_{k-1} are read once (nontemporal loads, nontemporal stores of the result); the row's own x_k
+// was gathered through the diagonal block a moment ago.  Every epilogue access is under the store's
+// guards (row < nbrows, b0 + q < nblk_total).
+template <int B, int MB>
+__global__ __launch_bounds__(256) void k_spmm_blk_mv8_cheb(i64 nbrows, i64 nslices, const i64 *__restrict__ slice_ptr,
+                                                           const double *__restrict__ val,
+                                                           const i32 *__restrict__ col, const double *__restrict__ Xk,
+                                                           double *__restrict__ Xold, i64 n, int nblk_total,
+                                                           int xcd_map, const double *__restrict__ Bv,
+                                                           const double *__restrict__ dinv, double omega, double gamma)
+{
+  const int wave = threadIdx.x >> 6, L = threadIdx.x & 63;
+  const int cp = L & 3;
+  const int ri = wave * 16 + (L >> 2);
+  const int b0 = blockIdx.y * MB;
+  const BlkSliceWalk w = blk_slice_walk(nslices, xcd_map);
+  for (i64 s = w.s0; s < w.s1; s += w.step)
+  {
+    double2 acc[MB][B];
+    spmm_blk_row<B, MB>(slice_ptr, val, col, Xk, n, nblk_total, b0, s, ri, cp, acc);
+    const i64 row = s * 64 + ri;
+    if (row < nbrows)
+    {
+      double gd[B];
+#pragma unroll
+      for (int r = 0; r < B; ++r) gd[r] = gamma * __builtin_nontemporal_load(dinv + row * B + r);
+#pragma unroll
+      for (int q = 0; q < MB; ++q)
+        if (b0 + q < nblk_total)
+        {
+          const i64 at = ((i64)(b0 + q) * n + row * B) * 8 + 2 * cp;
+          dv2 xk[B], bb[B], xo[B];
+#pragma unroll
+          for (int r = 0; r < B; ++r)
+          {
+            xk[r] = *reinterpret_cast<const dv2 *>(Xk + at + r * 8);
+            bb[r] = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(Bv + at + r * 8));
+            xo[r] = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(Xold + at + r * 8));
+          }
+#pragma unroll
+          for (int r = 0; r < B; ++r)
+          {
+            const double o0 = omega * (xk[r].x + gd[r] * (bb[r].x - acc[q][r].x) - xo[r].x) + xo[r].x;
+            const double o1 = omega * (xk[r].y + gd[r] * (bb[r].y - acc[q][r].y) - xo[r].y) + xo[r].y;
+            __builtin_nontemporal_store(dv2{o0, o1}, reinterpret_cast<dv2 *>(Xold + at + r * 8));
+          }
+        }
+    }
+  }
+}
+
 // column blocks per workgroup of k_spmm_blk_mv8<B, .>: the most that keep the kernel at 4 waves per
 // SIMD (<= 128 VGPRs) without scratch (DESIGN.md "Blocked SpMM")
 template <int B>
@@ -178,17 +257,58 @@ constexpr int spmm_blk_mb()
   return B == 4 ? 2 : 4;
 }
 
+// grid.x of the blocked product kernels and whether they walk the XCD shares
+static int spmm_blk_grid_x(const eig_mat_s &A, bool &xcd)
+{
+  static const bool flat = std::getenv("EIGMI_SPMM_BLK_FLAT") != nullptr;  // A/B: the plain grid stride
+  // XCD shares need a grid of whole groups of 8 and at least a slice per workgroup
+  xcd = !flat && A.nslices >= 64;
+  int gx = grid_for(A.nslices, 1, kStreamBlocks);
+  if (xcd) gx = std::min(kStreamBlocks, (gx + 7) / 8 * 8);
+  return gx;
+}
+
 template <int B, int MB>
 static void launch_spmm_blk_mb(const eig_mat_s &A, int nblk, const double *Qin, double *Qout, hipStream_t s)
 {
   const int gy = (nblk + MB - 1) / MB;
-  static const bool flat = std::getenv("EIGMI_SPMM_BLK_FLAT") != nullptr;  // A/B: the plain grid stride
-  // XCD shares need a grid of whole groups of 8 and at least a slice per workgroup
-  const bool xcd = !flat && A.nslices >= 64;
-  int gx = grid_for(A.nslices, 1, kStreamBlocks);
-  if (xcd) gx = std::min(kStreamBlocks, (gx + 7) / 8 * 8);
+  bool xcd;
+  const int gx = spmm_blk_grid_x(A, xcd);
   hipLaunchKernelGGL((k_spmm_blk_mv8<B, MB>), dim3(gx, gy), dim3(256), 0, s, A.nb_rows, A.nslices, A.slice_ptr, A.val,
                      A.col, Qin, Qout, A.nb_rows * B, nblk, xcd ? 1 : 0);
+}
+
+// The Chebyshev step on blocks: one launch for all column blocks (grid.y), the product's grid and
+// column blocks per workgroup (the epilogue's loads come after the product's value registers are dead:
+// DESIGN.md "Block Lanczos on blocks" has the register counts).
+template <int B>
+static void launch_cheb_blk(const eig_mat_s &M, int nblk, const double *Xk, double *Xold, const double *Bv,
+                            const double *dinv, double omega, double gamma, hipStream_t s)
+{
+  constexpr int MB = spmm_blk_mb<B>();
+  const int gy = (nblk + MB - 1) / MB;
+  bool xcd;
+  const int gx = spmm_blk_grid_x(M, xcd);
+  hipLaunchKernelGGL((k_spmm_blk_mv8_cheb<B, MB>), dim3(gx, gy), dim3(256), 0, s, M.nb_rows, M.nslices, M.slice_ptr,
+                     M.val, M.col, Xk, Xold, M.nb_rows * B, nblk, xcd ? 1 : 0, Bv, dinv, omega, gamma);
+}
+
+void launch_cheb_step_blk(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *Bv,
+                          const double *dinv, double omega, double gamma, hipStream_t s)
+{
+  const int nblk = (int)(m / 8);
+  EIG_CHECK(M.br == M.bc && M.br >= 2 && M.br <= 4, EIG_ERR_BLOCKSIZE, "blocked Chebyshev step: square blocks 2..4");
+  EIG_CHECK(!M.ctx->distributed(), EIG_ERR_ARG, "blocked Chebyshev step: single rank only");
+  EIG_CHECK(M.R == 1 && M.nb_rows == M.nb_cols, EIG_ERR_SHAPE, "blocked Chebyshev step: square matrix required");
+  EIG_CHECK(Xk != Xold, EIG_ERR_ARG, "blocked Chebyshev step: x_k must not be the output buffer");
+  if (nblk <= 0 || M.nb_rows <= 0) return;
+  switch (M.br)
+  {
+    case 2: launch_cheb_blk<2>(M, nblk, Xk, Xold, Bv, dinv, omega, gamma, s); break;
+    case 3: launch_cheb_blk<3>(M, nblk, Xk, Xold, Bv, dinv, omega, gamma, s); break;
+    default: launch_cheb_blk<4>(M, nblk, Xk, Xold, Bv, dinv, omega, gamma, s); break;
+  }
+  EIG_HIP(hipGetLastError());
 }
 
 // One instantiation per block size, also for a narrow product: instantiations with 1 / 2 column

@@ -801,6 +801,9 @@ def panel_gram_mv8(ctx, n, m1, m2, Q1, Q2, G):
 
 
 def mass_solve_mv8(M, m, degree, B, X, lmin=0.5, lmax=2.5):
+    """X = M^-1 B by `degree` Chebyshev-Jacobi steps (eig_mass_solve_mv8).  M: 1x1 blocks, or square
+    blocks 2..4 on one rank -- then B and X have M.info.n = nb_rows * b scalar rows and [lmin, lmax]
+    bound the spectrum of D^-1 M with D the scalar diagonal of the diagonal blocks (point Jacobi)."""
     M.ctx.check(lib.eig_mass_solve_mv8(M.h, m, degree, lmin, lmax, B.ptr, X.ptr))
 
 
@@ -984,7 +987,10 @@ class Multigrid:
 
 
 class BlockLanczos:
-    """eig_blanczos_t: block Lanczos for K x = lambda M x (config C5), see include/eigmi.h."""
+    """eig_blanczos_t: block Lanczos for K x = lambda M x (config C5), see include/eigmi.h.
+    K, M (and Ks): 1x1 blocks, or the same square blocks b = 2..4 on one rank (not with mg): vectors
+    have K.info.n = nb_rows * b scalar rows, the Chebyshev solve is point Jacobi on the scalar diagonal
+    of the diagonal blocks; other block shapes raise EigShapeError (EIG_ERR_BLOCKSIZE)."""
 
     def __init__(self, K, M, block=32, max_steps=8, degree=36, lmin=0.5, lmax=2.5, seed=123, Ks=None, sigma=0.0,
                  mg=None, cycles=0):

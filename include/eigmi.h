@@ -241,7 +241,9 @@ int eig_mat_get_info(eig_mat_t mat, eig_mat_info *info);
 int eig_lanczos_kernel_info(eig_mat_t mat, int fused, char *name, int name_len, int64_t *bytes);
 /* Kernel family a whole-matrix launch of `op` picks on this matrix image (its creation flags
  * included): EIG_OP_SPMV (eig_mv), EIG_OP_LANCZOS_K1, EIG_OP_LANCZOS_FUSED,
- * EIG_OP_SPMM8 (eig_spmm_mv8, per 8-column block), EIG_OP_CHEB8 (eig_mass_solve_mv8's step). */
+ * EIG_OP_SPMM8 (eig_spmm_mv8, per 8-column block), EIG_OP_CHEB8 (eig_mass_solve_mv8's step).
+ * EIG_OP_CHEB8 / EIG_OP_CHEB32 describe 1x1 images only ("none" on blocks, although
+ * eig_mass_solve_mv8 takes square blocks 2..4: its step there is k_spmm_blk_mv8_cheb). */
 enum { EIG_OP_SPMV = 0, EIG_OP_LANCZOS_K1 = 1, EIG_OP_LANCZOS_FUSED = 2, EIG_OP_SPMM8 = 3, EIG_OP_CHEB8 = 4,
        EIG_OP_SPMM32 = 5, EIG_OP_CHEB32 = 6 /* m % 32 == 0: the 3-D box-stencil kernel where it applies */ };
 int eig_mat_kernel_info(eig_mat_t mat, int op, char *name, int name_len);
@@ -651,7 +653,14 @@ int eig_arnoldi_shift_invert(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma
  *   M-inner product (panel V^T (M Z) on MFMA);  CholQR2:  Z = V_{j+1} B_{j+1}.
  * K and M: same rows / column window (shared pattern, e.g. eig_gen kinds 6 and 7), 1x1 blocks;
  * with a communicator, row-partitioned (eig_mat_create_bcsr_dist) and every panel allreduced.
- * The start block is mt19937(seed) normal numbers in MultiVector fill order (eigensolver.hh:49-55). */
+ * Square blocks FieldMatrix<double,b,b>, b = 2..4, on one rank as well (K, M and Ks with the same b;
+ * rectangular or differing blocks, or blocks on a distributed context: EIG_ERR_BLOCKSIZE): every
+ * vector then has n = nb_rows * b scalar rows (the (max_steps + 1) * block <= n check, the start block,
+ * eig_blanczos_ritz's vectors), the products run on the blocked image, and the Chebyshev-Jacobi solve
+ * is POINT Jacobi: D is the scalar diagonal of the diagonal blocks, so [lmin, lmax] bound the spectrum
+ * of that D^-1 M (D^-1 Ks).  eig_blanczos_create_si_mg stays 1x1 (eig_mg_create refuses blocks).
+ * The start block is mt19937(seed) normal numbers in MultiVector fill order over the global scalar
+ * rows (eigensolver.hh:49-55). */
 typedef struct eig_blanczos_s *eig_blanczos_t;
 typedef struct eig_blanczos_timing {
   double total_ms;   /* device time of the step batch (events, first to last) */
@@ -660,7 +669,8 @@ typedef struct eig_blanczos_timing {
   double orth_ms;    /* two CGS passes: M SpMM + MFMA panel Gram + panel update */
   double norm_ms;    /* CholQR2: 2 x (M SpMM + Gram + host 32x32 Cholesky + triangular update) */
   int64_t steps;
-  int64_t cheb_launches; /* fused Chebyshev kernel launches (one per 32 columns per Chebyshev step) */
+  int64_t cheb_launches; /* fused Chebyshev kernel launches (one per 32 columns per Chebyshev step; on
+                            square blocks 2..4 one per Chebyshev step, whatever the block width) */
   int64_t cholqr_recomputed; /* CholQR2 second passes (since creation) that recomputed M Z because the
                                 first pass's R was ill-conditioned (diagonal spread > 1e4) */
 } eig_blanczos_timing;
@@ -704,7 +714,9 @@ int eig_blanczos_ritz(eig_blanczos_t ws, int nev, int which, double *eval_host, 
 int eig_blanczos_tmatrix(eig_blanczos_t ws, int *dim, double *T_host);
 int eig_blanczos_destroy(eig_blanczos_t ws);
 /* X = M^-1 B for m columns (window layout) by `degree` Chebyshev-Jacobi steps (the operator's solve);
- * X must not alias B (EIG_ERR_ARG). */
+ * X must not alias B (EIG_ERR_ARG).  M square with 1x1 blocks, or (one rank) square blocks
+ * FieldMatrix<double,b,b>, b = 2..4: then B and X have n = nb_rows * b scalar rows and the splitting is
+ * point Jacobi on the scalar diagonal of the diagonal blocks ([lmin, lmax] bound that D^-1 M). */
 int eig_mass_solve_mv8(eig_mat_t M, int64_t m, int degree, double lmin, double lmax, const double *B, double *X);
 /* Tall-skinny panel kernels on n-row MultiVector<double,8> buffers (single rank):
  * Y = beta Y + alpha Q S (Q n x m1, S m1 x m2 row-major device, m2 in {8,16,24,32}; Y may be Q), and

@@ -6,7 +6,9 @@
   C2  3-D Poisson 128^3: SpMV (cache-resident: 217 MB < 256 MB MALL), Lanczos step, the b = 8
       SpMM, block Gram-Schmidt (m = 8, 32) and one StandardLargest iteration vs the CPU path
   C3  3-D Q1 elasticity 64^3, 3x3 blocks: BCSR SpMV against 76 nnzb + 4 (nb+1) + 48 nb bytes, the
-      blocked SpMM, and the Lanczos step on blocks (two-kernel and fused, alternated twice)
+      blocked SpMM, the Lanczos step on blocks (two-kernel and fused, alternated twice), and the
+      blocked pencil K, M = D + 0.3 (K - D): the Chebyshev step k_spmm_blk_mv8_cheb (m = 8, 32)
+      beside the same run's product, and the block Lanczos k = 32 step's phase split
   INV inverse iteration with exported LU factors on the harness matrices:
       matmul_inverse_tallskinny_blocked (m = 8), StandardInverse, GeneralizedInverse (GenEO pencil)
       and computeGenSymShiftInvertMinMagnitude, GPU vs the oracle / scipy ARPACK on the host
@@ -338,6 +340,63 @@ def c3(ctx):
                  kernel_frac=round(ws.kernel_bytes / (kus * 1e-6) / 1e9 / PEAK, 4), mv_us=round(mv_ms * 1e3, 2),
                  step_vs_mv=round(t.total_ms / steps / mv_ms, 4), kernel_vs_mv=round(kus * 1e-3 / mv_ms, 4), **extra)
             ws.close()
+    c3_pencil(ctx, M, rp, c, v, nb, nnzb)
+
+
+def c3_pencil(ctx, K, rp, c, v, nb, nnzb):
+    """The blocked pencil of C3: K = q1elast(64) and M = D + 0.3 (K - D) built on the host (D the scalar
+    diagonal of K, constant 16/3: same pattern, bitwise symmetric, spec(D^-1 M) = 0.7 + 0.3 spec(D^-1 K)
+    inside the default Chebyshev bounds [0.5, 2.5]).  The Chebyshev step k_spmm_blk_mv8_cheb from the
+    difference of two solve degrees beside the same run's blocked product, and the block step's split."""
+    n = 3 * nb
+    cfg = "C3 Q1 elasticity 64^3 3x3 BCSR"
+    v3 = v.reshape(-1, 3, 3)
+    dg = np.nonzero(c == np.repeat(np.arange(nb), np.diff(rp)))[0][:, None]
+    r = np.arange(3)
+    vm = 0.3 * v3
+    vm[dg, r, r] = v3[dg, r, r]
+    M = eigmi.Matrix.from_bcsr(ctx, rp, c, vm.reshape(-1), 3, 3)
+    d0, d1 = 2, 22
+    for m in (8, 32):
+        B, X, R = ctx.array(oracle.random_mv8(n, m, 2)), ctx.zeros(n * m), ctx.zeros(n * m)
+        # the tool's own check of the solve at the degree the block step uses
+        eigmi.mass_solve_mv8(M, m, 36, B, X)
+        eigmi.spmm_blk_mv8(M, m, X, R)
+        bh = B.get()
+        resid = float(np.linalg.norm(bh - R.get()) / np.linalg.norm(bh))
+        assert resid <= 1e-12, f"mass solve residual {resid:.2e} at degree 36"
+        eigmi.spmm_blk_mv8(K, m, B, R)
+        ctx.sync()
+
+        def spmm_batch(reps=20):
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                eigmi.spmm_blk_mv8(M, m, B, R)
+            ctx.sync()
+            return (time.perf_counter() - t0) / reps
+        ts = min(spmm_batch() for _ in range(3))
+        t0 = min(wall(lambda: (eigmi.mass_solve_mv8(M, m, d0, B, X), ctx.sync()), 5)[0] for _ in range(3))
+        t1 = min(wall(lambda: (eigmi.mass_solve_mv8(M, m, d1, B, X), ctx.sync()), 5)[0] for _ in range(3))
+        tc = (t1 - t0) / (d1 - d0)
+        sb = 76 * nnzb + 4 * (nb + 1) + 2 * 8 * m * n   # the product
+        add = 2 * 8 * m * n + 8 * n                     # b and x_{k-1}, dinv (the row's own x_k from L2)
+        emit(config=cfg, op=f"blocked Chebyshev step m={m}", kernel="k_spmm_blk_mv8_cheb", us=round(tc * 1e6, 2),
+             algorithmic_bytes=sb + add, GBs=round((sb + add) / tc / 1e9, 1), frac=round((sb + add) / tc / 1e9 / PEAK, 4),
+             spmm_us=round(ts * 1e6, 2), spmm_GBs=round(sb / ts / 1e9, 1),
+             spmm_plus_1p5_added_us=round(ts * 1e6 * (1.0 + 1.5 * add / sb), 2), degree36_residual=resid)
+        B.free(), X.free(), R.free()
+    steps, warm, b, degree = 4, 1, 32, 36
+    bl = eigmi.BlockLanczos(K, M, block=b, max_steps=steps + warm, degree=degree, seed=123)
+    bl.step(warm)
+    t = bl.step(steps)
+    ev, _, _ = bl.ritz(4, eigmi.WHICH_LA, want_resid=False)
+    emit(config=cfg, op=f"block Lanczos k={b} step (Chebyshev degree {degree}, CGS2, CholQR2)",
+         ms_per_step=round(t.total_ms / steps, 2), kspmm_ms=round(t.kspmm_ms / steps, 2),
+         cheb_ms=round(t.cheb_ms / steps, 2), orth_ms=round(t.orth_ms / steps, 2), norm_ms=round(t.norm_ms / steps, 2),
+         cheb_launches=int(t.cheb_launches), cheb_kernel_us=round(t.cheb_ms / t.cheb_launches * 1e3, 1),
+         top_ritz=[float(x) for x in ev], steps_taken=steps + warm)
+    bl.close()
+    M.close()
 
 
 def inv(ctx):
