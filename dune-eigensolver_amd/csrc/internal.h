@@ -281,13 +281,13 @@ struct eig_mat_s {
   eigmi::i64 sym_pack_bytes = 0;
   // SELL image: padded entries of the explicit-column slices (their 4-B column indices are streamed)
   eigmi::i64 sell_explicit = 0;
-  // Plane-march split of a distributed slab (k_spmv.hip march_plan): planes [mz0, mz1) have no
+  // Plane-march split of a distributed slab (march_plan.cpp march_plan): planes [mz0, mz1) have no
   // ghost columns and are marched while the halo is in flight; march_bnd lists every slice outside
   // them (the boundary launch after the exchange).  mz1 <= mz0: no split.
   eigmi::i64 mz0 = 0, mz1 = 0;
   int tune_march_runs = 0;  // eig_mat_tune(EIG_TUNE_MARCH_RUNS): plane runs per column, 0 = automatic
   int tune_halo_whole = 0;      // eig_mat_tune(EIG_TUNE_HALO): 1 = exchange first, then one whole launch
-  int tune_march_prefetch = 0;  // eig_mat_tune(EIG_TUNE_MARCH_PREFETCH): asks march_select (k_spmv.hip) for a variant of march_variants.h, 0 = automatic
+  int tune_march_prefetch = 0;  // eig_mat_tune(EIG_TUNE_MARCH_PREFETCH): asks march_select (march_plan.cpp) for a variant of march_variants.h, 0 = automatic
   int tune_cache = 0;           // eig_mat_tune(EIG_TUNE_CACHE): cache-policy bits of the march streams (measurement)
   int tune_box_cols = 0;    // eig_mat_tune(EIG_TUNE_BOX_COLS): columns per box-image workgroup (16 / 32), 0 = automatic
   int tune_box_map = 0;     // eig_mat_tune(EIG_TUNE_BOX_MAP): 1 = XCD-contiguous tile map of k_box_mv32 (measurement)
@@ -377,7 +377,8 @@ void launch_lanczos_pipe(const eig_mat_s &A, double *T, double *UZ, const double
                          double *out, hipStream_t s, ReduceWS red);
 // beta / nsum of the current logical step after a repair launch (L = the next launch index)
 void launch_fused_tail(const LanczosState &st, int L, hipStream_t s);
-// Plane march (k_spmv.hip): band geometry (widest offset D) and whether the interior-plane split
+// Plane march (kernels and launchers: k_spmv.hip; selection, plans and queries: march_plan.h / march_plan.cpp):
+// band geometry (widest offset D) and whether the interior-plane split
 // launch applies now (split built at upload, image and EIGMI_* switches allow it).  Passing
 // slices == &kMarchInteriorTag to launch_spmv / launch_lanczos_spmv / launch_lanczos_fused marches
 // planes [A.mz0, A.mz1).

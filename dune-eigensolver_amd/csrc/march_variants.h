@@ -1,7 +1,7 @@
 // The plane-march variants (k_spmv.hip): what each variant number IS, in one table.  The kernels'
-// `if constexpr`s and __launch_bounds__, the launch dispatch, the selection (march_select), the
-// run-count rules of march_plan and the byte model of lanczos_kernel_info all read it; adding or
-// retiring a variant is one row here plus its entry in MarchDispatch.  The numbers are public
+// `if constexpr`s and __launch_bounds__ and the launch dispatch (k_spmv.hip), the selection (march_select),
+// the run-count, direction and body rules of march_plan and the byte model of lanczos_kernel_info
+// (march_plan.cpp) all read it; adding or retiring a variant is one row here plus its entry in MarchDispatch.  The numbers are public
 // (eig_mat_info.march_variant, the profiler's kernel instance names) and do not change.
 // Plain C++17: no HIP headers, so host tests include it as it is.
 #pragma once
@@ -40,6 +40,10 @@ struct MarchTraits {
   int wide_runs;     // fused step on wide planes (>= 1024 columns): at most this many plane runs per column
   bool wide_two;     // fused step on wide planes: two plane runs per column (march_plan)
   bool line_groups;  // takes the 4-line workgroup mapping (EIG_TUNE_MARCH_LINES)
+  // the 2-line kernels that also hold the downward body (MarchPlan::down; 24 spills marching upward alone)
+  bool down_body;
+  // ... whose fused kernel also holds the pipelined bodies (MarchPlan::pipe; 24 keeps the plain body)
+  bool pipe_body;
 
   // whole planes: every marched row exists, no row test
   constexpr bool whole_planes() const { return family != kMarchMasked; }
@@ -76,9 +80,10 @@ constexpr MarchTraits value(int val, int fused_waves, bool line_groups, bool wid
   return {true, kMarchGeo2, 0, false, val, false, false, val == 5 ? kMarchPack : kMarchArrays, true, 8, fused_waves,
           8, wide_two, line_groups};
 }
-constexpr MarchTraits two_line(int fused_waves)
+constexpr MarchTraits two_line(int fused_waves, bool down_body, bool pipe_body)
 {
-  return {true, kMarchGeo2L2, 0, false, 0, false, false, kMarchPack, true, 5, fused_waves, 8, true, false};
+  return {true, kMarchGeo2L2, 0, false, 0, false, false, kMarchPack, true, 5, fused_waves, 8, true, false,
+          down_body, pipe_body};
 }
 constexpr MarchTraits kuhn(bool kp, bool lx, int fused_waves)
 {
@@ -111,9 +116,9 @@ constexpr MarchTraits kMarchTable[kMarchVariantEnd] = {
     /* 19 */ march_kind::kuhn(true, false, 5),             // 16 built for 5 waves per SIMD
     /* 20 */ march_kind::kuhn(true, true, 4),              // Kuhn pack march with the line exchange in LDS
     /* 21 */ march_kind::unused(),
-    /* 22 */ march_kind::two_line(5),                      // value pack, two grid lines per wave
-    /* 23 */ march_kind::two_line(4),                      // 22 built for 4 waves per SIMD
-    /* 24 */ march_kind::two_line(6),                      // 22 built for 6 waves per SIMD
+    /* 22 */ march_kind::two_line(5, true, true),          // value pack, two grid lines per wave
+    /* 23 */ march_kind::two_line(4, true, true),          // 22 built for 4 waves per SIMD
+    /* 24 */ march_kind::two_line(6, false, false),        // 22 built for 6 waves per SIMD: the upward plain body alone
 };
 
 constexpr MarchTraits march_traits(int variant)

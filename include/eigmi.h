@@ -283,7 +283,7 @@ enum { EIG_TUNE_MARCH_RUNS = 1, EIG_TUNE_BOX_SEGS = 2, EIG_TUNE_MARCH_PREFETCH =
  * to its first -- eig_mv and the classic step too where EIG_TUNE_MARCH_PREFETCH 16 / 17 routes them
  * there (tests and A/B only); both bits (24) = fused launches alternate, downward when the launch
  * index is odd, whatever the built-in default is.  Neither bit: the default (kMarch2lSerpentine in
- * k_spmv.hip).
+ * march_plan.h).
  * Pipelined body of the fused launches of variants 22 / 23 (every plane loaded through LDS one plane
  * ahead; 104 KiB of LDS per workgroup; alpha and beta bitwise unchanged): by default on where the launch
  * has at most one workgroup per CU anyway (two plane runs on planes of at least 1024 columns) and, where

@@ -1,17 +1,30 @@
-// Host-side unit checks of the plane-march variant table (csrc/march_variants.h) and of the selection
-// (k_spmv.hip march_select / kuhn_variant).  No GPU: only the selection functions run.
+// Host-side unit checks of the plane-march variant table (csrc/march_variants.h) and of the selection and
+// planning (csrc/march_plan.cpp, compiled with this file: march_select / kuhn_variant / march_plan /
+// marchg_plan / lanczos_kernel_info / kernel_for).  No GPU and no library: plain host code.
 //  * the traits of every variant against literal lists (waves, family arguments, pack, byte model);
 //  * the P1 Kuhn value-pack variants read the pack through one 32-bit buffer descriptor of 64 B per
 //    row, so a grid with sym_ld * 64 >= 2^31 (2^25 rows and more) must take the band arrays (12);
 //  * for every image class, tune value 0..18 and both launch kinds the variant march_select returns,
-//    and that it is valid, dispatched and has its family's preconditions met on the image.
+//    and that it is valid, dispatched and has its family's preconditions met on the image;
+//  * the plans of march_plan (runs, items, variant, stores, direction, body, line groups, planes, far spans)
+//    and marchg_plan, and the kernel names and byte counts of the queries, against literals.
 #include <cstdio>
 #include <initializer_list>
 
+#include <string>
+
 #include "../../dune-eigensolver_amd/csrc/internal.h"
+#include "../../dune-eigensolver_amd/csrc/march_plan.h"
 #include "../../dune-eigensolver_amd/csrc/march_variants.h"
 
 using namespace eigmi;
+
+// The box-image queries of kernel_for live with their kernels (k_box.hip); this program is march_plan.cpp and
+// this file alone, and its images are no box images.
+namespace eigmi {
+bool box_prepare(const eig_mat_s &) { return false; }
+int box_cols(const eig_mat_s &) { return 32; }
+}  // namespace eigmi
 
 // ---- the table ---------------------------------------------------------------------------------
 constexpr bool in(int v, std::initializer_list<int> l)
@@ -90,6 +103,7 @@ constexpr bool classes_ok()
     if (t.wide_runs != (in(v, {0, 1, 2, 3, 4, 5, 6, 8, 9}) ? 6 : 8)) return false;
     if (t.wide_two != in(v, {12, 16, 19, 20, 15, 22, 23, 24})) return false;
     if (t.line_groups != in(v, {10, 11, 14, 15})) return false;
+    if (t.down_body != in(v, {22, 23}) || t.pipe_body != in(v, {22, 23})) return false;
   }
   return true;
 }
@@ -259,10 +273,217 @@ static void test_kuhn_pack_guard()
   }
 }
 
+// ---- the plans ---------------------------------------------------------------------------------
+// march_plan, marchg_plan and the kernel queries on images built as above, on a 256-CU device and one rank.
+// Every literal below is what the planning code computed before it moved out of k_spmv.hip.
+static double band_values[1];  // the plans only form addresses from sym_val
+static eig_ctx_s ctx256;
+
+static eig_mat_s plan_image(int nx, int ny, int nz, int nd)
+{
+  eig_mat_s A = grid_image(nx, ny, nz, nd);
+  ctx256.num_cu = 256;
+  A.ctx = &ctx256;
+  A.sym_val = band_values;
+  A.nslices = (A.nb_rows + 63) / 64;
+  return A;
+}
+static eig_mat_s uniform_image(int nx, int ny, int nz)
+{
+  eig_mat_s A = plan_image(nx, ny, nz, 7);
+  A.sym_uniform = true;
+  const double uc[4] = {6.0, -1.0, -2.0, -3.0};  // the arrays of the offsets 0, +1, +nx, +D
+  for (int j = 0; j < 4; ++j) A.sym_uc[j] = uc[j];
+  return A;
+}
+
+struct WantPlan {
+  int nseg, ncol, uni, tstore, down, pipe, lines;
+  long long zb, nplanes, D;
+  int dn, dq;
+};
+static void expect_plan(const char *name, const MarchPlan &mp, const WantPlan &w)
+{
+  const bool ok = mp.nseg == w.nseg && mp.ncol == w.ncol && mp.uni == w.uni && mp.tstore == w.tstore &&
+                  mp.down == w.down && mp.pipe == w.pipe && mp.lines == w.lines && mp.zb == w.zb &&
+                  mp.nplanes == w.nplanes && mp.D == w.D && mp.dn == w.dn && mp.dq == w.dq && mp.pack == nullptr;
+  if (ok) return;
+  std::printf("%s: plan {%d, %d, %d, %d, %d, %d, %d, %lld, %lld, %lld, %d, %d}%s\n", name, mp.nseg, mp.ncol, mp.uni,
+              mp.tstore, mp.down, mp.pipe, mp.lines, (long long)mp.zb, (long long)mp.nplanes, (long long)mp.D,
+              (int)mp.dn, (int)mp.dq, mp.pack ? " with a pack" : "");
+  ++bad;
+}
+// a plan that does not march is all zeros
+static const WantPlan kNoPlan = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+static void test_plans()
+{
+  // value 7-point 256^3, fused: the 2-line march on two runs of line pairs, 256 workgroups = num_cu: pipelined
+  eig_mat_s A = plan_image(256, 256, 256, 7);
+  expect_plan("value 256^3 fused", march_plan(A, kSymN8, 0, -1, true), {2, 512, 22, 0, 0, 1, 0, 0, 256, 65536, -256, 256});
+  expect_plan("value 256^3 eig_mv", march_plan(A, kSymN8), {8, 1024, 0, 0, 0, 0, 0, 0, 256, 65536, -256, 256});
+  ctx256.num_cu = 255;
+  expect_plan("value 256^3 fused, 255 CUs", march_plan(A, kSymN8, 0, -1, true),
+              {2, 512, 22, 0, 0, 0, 0, 0, 256, 65536, -256, 256});
+  ctx256.num_cu = 256;
+  A.tune_cache = 32;
+  expect_plan("value 256^3 fused, cache 32", march_plan(A, kSymN8, 0, -1, true),
+              {2, 512, 22, 0, 0, 0, 0, 0, 256, 65536, -256, 256});
+  A.tune_cache = 16;
+  expect_plan("value 256^3 fused, cache 16", march_plan(A, kSymN8, 0, -1, true),
+              {2, 512, 22, 0, 1, 1, 0, 0, 256, 65536, -256, 256});
+  A.tune_cache = 1;
+  expect_plan("value 256^3 fused, cache 1", march_plan(A, kSymN8, 0, -1, true),
+              {2, 512, 22, 1, 0, 1, 0, 0, 256, 65536, -256, 256});
+  A.tune_cache = 0;
+  // EIG_TUNE_MARCH_RUNS: taken as it is, lowered to what kMaxRedBlocks workgroups hold, never past the planes
+  A.tune_march_prefetch = 13;  // variant 15: 1024 items per run
+  A.tune_march_runs = 64;
+  expect_plan("value 256^3 fused, variant 15, 64 runs asked", march_plan(A, kSymN8, 0, -1, true),
+              {8, 1024, 15, 0, 0, 0, 0, 0, 256, 65536, -256, 256});
+  A.tune_march_runs = 5;
+  expect_plan("value 256^3 fused, variant 15, 5 runs asked", march_plan(A, kSymN8, 0, -1, true),
+              {5, 1024, 15, 0, 0, 0, 0, 0, 256, 65536, -256, 256});
+  A.tune_march_prefetch = 0;
+  A.tune_march_runs = 1000;
+  expect_plan("value 256^3 fused, 1000 runs asked", march_plan(A, kSymN8, 0, -1, true),
+              {16, 512, 22, 0, 0, 0, 0, 0, 256, 65536, -256, 256});
+  A.tune_march_runs = 0;
+  A.kflags |= EIG_MAT_NO_MARCH;
+  expect_plan("value 256^3 fused, EIG_MAT_NO_MARCH", march_plan(A, kSymN8, 0, -1, true), kNoPlan);
+  A.kflags = 0;
+  expect_plan("value 256^3 on the gather image mode", march_plan(A, kSym8, 0, -1, true), kNoPlan);
+
+  // below EIG_MARCH_PIPE_MIN_ROWS the automatic 2-line march keeps the plain bodies; asked for, it pipelines
+  A = plan_image(256, 256, 64, 7);
+  expect_plan("value 256 x 256 x 64 fused", march_plan(A, kSymN8, 0, -1, true),
+              {2, 512, 22, 0, 0, 0, 0, 0, 64, 65536, -256, 256});
+  A.tune_march_prefetch = 16;
+  expect_plan("value 256 x 256 x 64 fused, variant 22 asked", march_plan(A, kSymN8, 0, -1, true),
+              {2, 512, 22, 0, 0, 1, 0, 0, 64, 65536, -256, 256});
+
+  A = plan_image(128, 128, 128, 7);
+  expect_plan("value 128^3 fused", march_plan(A, kSymN8, 0, -1, true), {8, 256, 15, 1, 0, 0, 0, 0, 128, 16384, -128, 128});
+  expect_plan("value 128^3 eig_mv", march_plan(A, kSymN8), {32, 256, 0, 0, 0, 0, 0, 0, 128, 16384, -128, 128});
+  A.tune_march_prefetch = 16;  // the 2-line march on narrow planes: twice the runs of line pairs
+  expect_plan("value 128^3 fused, variant 22 asked", march_plan(A, kSymN8, 0, -1, true),
+              {16, 128, 22, 1, 0, 0, 0, 0, 128, 16384, -128, 128});
+
+  A = uniform_image(256, 256, 256);
+  expect_plan("uniform 256^3 fused", march_plan(A, kSymN8, 0, -1, true), {8, 1024, 7, 0, 0, 0, 0, 0, 256, 65536, -256, 256});
+  {
+    const MarchPlan mp = march_plan(A, kSymN8, 0, -1, true);
+    if (mp.cD != -3.0 || mp.c0 != 6.0 || mp.c1 != -1.0 || mp.cn != -2.0 || mp.cq != -2.0 || mp.gx != 256 || mp.gz != 256)
+      ++bad, std::printf("uniform 256^3: constants %g %g %g %g %g, grid %d %d\n", mp.cD, mp.c0, mp.c1, mp.cn, mp.cq, mp.gx, mp.gz);
+  }
+
+  A = plan_image(256, 256, 256, 15);
+  expect_plan("Kuhn 256^3 eig_mv", march_plan(A, kSymN32), {2, 1024, 20, 0, 0, 0, 0, 0, 256, 65536, -65792, 256});
+  expect_plan("Kuhn 256^3 fused", march_plan(A, kSymN32, 0, -1, true), {2, 1024, 20, 0, 0, 0, 0, 0, 256, 65536, -65792, 256});
+  {
+    // band array of every upper box offset, -1 where the Kuhn stencil stores none
+    const MarchPlan mp = march_plan(A, kSymN32);
+    const int kj[14] = {0, 1, -1, 2, 3, -1, -1, -1, -1, 4, 5, -1, 6, 7};
+    for (int q = 13; q < 27; ++q)
+      if (mp.kj[q] != kj[q - 13]) ++bad, std::printf("Kuhn 256^3: kj[%d] = %d, want %d\n", q, mp.kj[q], kj[q - 13]);
+  }
+
+  A = plan_image(64, 64, 64, 7);
+  A.tune_march_lines = 4;
+  expect_plan("value 64^3 fused, line groups", march_plan(A, kSymN8, 0, -1, true), {32, 64, 15, 1, 0, 0, 4, 0, 64, 4096, -64, 64});
+  A.tune_march_prefetch = 15;
+  expect_plan("value 64^3 fused, variant 18, line groups asked", march_plan(A, kSymN8, 0, -1, true),
+              {32, 64, 18, 1, 0, 0, 0, 0, 64, 4096, -64, 64});
+  A.tune_march_prefetch = 16;
+  A.tune_march_lines = 0;
+  A.tune_cache = 64;  // the pipelined body wherever it can run
+  expect_plan("value 64^3 fused, variant 22, cache 64", march_plan(A, kSymN8, 0, -1, true),
+              {64, 32, 22, 1, 0, 1, 0, 0, 64, 4096, -64, 64});
+  A.tune_cache = 0;
+  A.tune_march_prefetch = 0;
+  // interior planes of a slab: from 2 planes on
+  expect_plan("value 64^3 fused, planes [1, 3)", march_plan(A, kSymN8, 1, 3, true), {2, 64, 15, 1, 0, 0, 0, 1, 2, 4096, -64, 64});
+  expect_plan("value 64^3 eig_mv, planes [1, 3)", march_plan(A, kSymN8, 1, 3), {2, 64, 0, 0, 0, 0, 0, 1, 2, 4096, -64, 64});
+  expect_plan("value 64^3 fused, planes [1, 2)", march_plan(A, kSymN8, 1, 2, true), kNoPlan);
+  // the SpMM march: 16-row columns
+  expect_plan("value 64^3, chunk 16", march_plan(A, kSymN8, 0, -1, false, 16), {32, 256, 0, 0, 0, 0, 0, 0, 64, 4096, -64, 64});
+  // a whole matrix marches from 4 planes on
+  A = plan_image(64, 64, 3, 7);
+  expect_plan("value 64 x 64 x 3 fused", march_plan(A, kSymN8, 0, -1, true), kNoPlan);
+  expect_plan("value 64 x 64 x 3 eig_mv", march_plan(A, kSymN8), kNoPlan);
+}
+
+static void test_marchg_plan()
+{
+  // the Kuhn band: the carried offset is the widest multiple of 16 whose four spans hold at most kGSpan offsets
+  eig_mat_s A = plan_image(64, 64, 64, 15);
+  MarchPlan mp;
+  GSpans sp;
+  const bool ok = marchg_plan(A, mp, sp);
+  const int want[10] = {3, 11, 0, 3, 4, 6, 9, 11, 12, 15};
+  const int got[10] = {sp.kPm, sp.kPp, sp.s1b, sp.s1e, sp.s2b, sp.s2e, sp.s3b, sp.s3e, sp.s4b, sp.s4e};
+  bool same = ok;
+  for (int k = 0; k < 10; ++k) same = same && got[k] == want[k];
+  if (!same || mp.D != 4096 || mp.ncol != 256 || mp.nseg != 24 || mp.nplanes != 64 || mp.zb != 0 || mp.mrows != 64 * 4096)
+  {
+    ++bad;
+    std::printf("marchg Kuhn 64^3: %d, P %lld ncol %d nseg %d nplanes %lld mrows %lld, spans", (int)ok, (long long)mp.D,
+                mp.ncol, mp.nseg, (long long)mp.nplanes, (long long)mp.mrows);
+    for (int k = 0; k < 10; ++k) std::printf(" %d", got[k]);
+    std::printf("\n");
+  }
+  // the same band without its -1 offset does not qualify
+  for (int k = 6; k < 14; ++k) A.sym_off[k] = A.sym_off[k + 1], A.sym_dj[k] = A.sym_dj[k + 1];
+  A.sym_nd = 14;
+  if (A.sym_off[6] != 0 || marchg_plan(A, mp, sp)) ++bad, std::printf("marchg: a band without -1 qualified\n");
+  A = plan_image(64, 64, 64, 15);
+  A.kflags |= EIG_MAT_NO_MARCH;
+  if (marchg_plan(A, mp, sp)) ++bad, std::printf("marchg: EIG_MAT_NO_MARCH ignored\n");
+}
+
+static void expect_info(const char *name, const eig_mat_s &A, bool fused, const char *want_name, long long want_bytes)
+{
+  std::string got;
+  i64 bytes = 0;
+  lanczos_kernel_info(A, fused, got, bytes);
+  if (got != want_name || bytes != want_bytes || kernel_for(A, fused ? 2 : 1) != want_name)
+    ++bad, std::printf("%s: %s, %lld bytes\n", name, got.c_str(), (long long)bytes);
+}
+
+static void test_kernel_info()
+{
+  const long long n256 = 256LL * 256 * 256;
+  eig_mat_s A = plan_image(256, 256, 256, 7);
+  expect_info("value 256^3 fused", A, true, "k_lanczos_fused_march", 8 * 4 * n256 + 32 * n256);    // the pack's 4 arrays
+  expect_info("value 256^3 K1", A, false, "k_lanczos_spmv_march", 8 * 4 * n256 + n256 + 24 * n256);  // arrays and masks
+  if (kernel_for(A, 0) != "k_spmv_march" || kernel_for(A, 3) != "k_spmm8_march" || kernel_for(A, 4) != "k_spmm8_marchg_cheb")
+    ++bad, std::printf("value 256^3: %s %s %s\n", kernel_for(A, 0).c_str(), kernel_for(A, 3).c_str(), kernel_for(A, 4).c_str());
+  A.kflags |= EIG_MAT_NO_MARCH;
+  expect_info("value 256^3 fused, no march", A, true, "k_lanczos_fused_b1", 8 * 4 * n256 + n256 + 32 * n256);
+  expect_info("value 256^3 K1, no march", A, false, "k_lanczos_spmv_b1", 8 * 4 * n256 + n256 + 24 * n256);
+  if (kernel_for(A, 0) != "k_spmv_b1" || kernel_for(A, 3) != "k_sell_mv8g" || kernel_for(A, 4) != "k_sell_mv8q_cheb")
+    ++bad, std::printf("value 256^3, no march: %s %s %s\n", kernel_for(A, 0).c_str(), kernel_for(A, 3).c_str(), kernel_for(A, 4).c_str());
+  A = uniform_image(256, 256, 256);
+  expect_info("uniform 256^3 fused", A, true, "k_lanczos_fused_march", 32 * n256);  // the vectors alone
+  expect_info("uniform 256^3 K1", A, false, "k_lanczos_spmv_march", 24 * n256);
+  A = plan_image(256, 256, 256, 15);
+  expect_info("Kuhn 256^3 fused", A, true, "k_lanczos_fused_march", 8 * 8 * n256 + 32 * n256);
+  expect_info("Kuhn 256^3 K1", A, false, "k_lanczos_spmv_march", 8 * 8 * n256 + 24 * n256);
+  if (kernel_for(A, 3) != "k_spmm8_marchg") ++bad, std::printf("Kuhn 256^3 SpMM: %s\n", kernel_for(A, 3).c_str());
+  // the queries build nothing
+  if (march_variant(A, true) != 20 || march_pipe(A) != 0 || A.sym_pack) ++bad, std::printf("Kuhn 256^3: queries\n");
+  A = plan_image(256, 256, 256, 7);
+  if (march_variant(A, true) != 22 || march_variant(A, false) != 0 || march_pipe(A) != 1 || march_split_active(A) || A.sym_pack)
+    ++bad, std::printf("value 256^3: queries\n");
+}
+
 int main()
 {
   test_kuhn_pack_guard();
   test_selection();
+  test_plans();
+  test_marchg_plan();
+  test_kernel_info();
   std::printf(bad ? "FAILED\n" : "ALL OK\n");
   return bad ? 1 : 0;
 }
