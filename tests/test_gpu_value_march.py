@@ -11,6 +11,7 @@ conductance per grid edge), 7-point Poisson with EIG_MAT_NO_UNIFORM, and random 
 import numpy as np
 import pytest
 
+import box_grids
 import eigmi
 import oracle
 
@@ -343,3 +344,45 @@ def test_kuhn_box_march(ctx, kind, N):
     fa, fb, _ = eigmi.lanczos_run(M, 15, seed=123, fused=True)
     qa, qb = oracle.lanczos_fused(A, oracle.random_vec(n, 123), 15)
     assert np.allclose(fa, qa, rtol=1e-12, atol=0) and np.allclose(fb, qb, rtol=1e-12, atol=0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,variant", [((64, 10, 7), 16), ((64, 12, 6), 20), ((128, 9, 5), 16)],
+                         ids=["64x10x7", "64x12x6", "128x9x5"])
+def test_kuhn_box_march_noncubic(ctx, dims, variant):
+    """The Kuhn 15-point march on boxes with gx != gy != gz (tests/box_grids.py, one value per grid
+    edge): the automatic variant is 20 (line exchange in LDS) only where the lines come in groups of
+    4 (gy = 12), else 16 (gy = 10, 9); 128 x 9 x 5 has two 64-x runs per line and an odd line count.
+    eig_mv bitwise the reference row loop on every variant (0: automatic, 13: 16, 14: 12, 1: the row
+    kernels) and plane-run count; 20 fused and 20 classic steps within 1e-12 of their restatements
+    and of the row kernels, as test_kuhn_box_march holds on cubes."""
+    A = box_grids.box_matrix(dims, "kuhn15", "edge", seed=sum(dims))
+    n = A.n
+    M = eigmi.Matrix.from_bcsr(ctx, A.rowptr, A.col, A.val)
+    info = M.info
+    assert info.sym_offsets == 15 and info.march_variant == variant, (info.sym_offsets, info.march_variant)
+    assert M.lanczos_kernel_info(True)[0] == "k_lanczos_fused_march"
+    x = np.random.default_rng(13).standard_normal(n)
+    ref = oracle.csr_mv(A, x)
+    U0 = oracle.random_vec(n, 123)
+    qa, qb = oracle.lanczos_fused(A, U0, 20)
+    _, ra, rb = oracle.lanczos(A, U0, 20)
+    base = {}
+    for pf in (1, 0, 13, 14):
+        M.tune(march_prefetch=pf)
+        assert M.info.march_variant == {1: -1, 0: variant, 13: 16, 14: 12}[pf], pf
+        for runs in (0, 1, 3):
+            M.tune(runs)
+            assert np.array_equal(M.mv_host(x), ref), (pf, runs)
+            for fused in (False, True):
+                a, b, _ = eigmi.lanczos_run(M, 20, seed=123, fused=fused)
+                oa, ob = (qa, qb) if fused else (ra, rb)
+                assert np.allclose(a, oa, rtol=1e-12, atol=0) and np.allclose(b, ob, rtol=1e-12, atol=0), \
+                    (pf, runs, fused)
+                if pf == 1:
+                    base.setdefault(fused, (a, b))
+                else:
+                    assert np.allclose(a, base[fused][0], rtol=1e-12, atol=0) and \
+                        np.allclose(b, base[fused][1], rtol=1e-12, atol=0), (pf, runs, fused)
+    M.tune(0, march_prefetch=0)
+    M.close()

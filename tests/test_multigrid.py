@@ -9,10 +9,13 @@ per iteration with the default smoother) to 1e-12; the operator is symmetric to 
 Lanczos needs a self-adjoint OP); the 4 smallest eigenvalues at N = 24 within 1e-8 of ARPACK
 shift-invert (scipy eigsh sigma = 0, exact factorisation), as test_shift_invert_smallest_p1 holds
 the Chebyshev-Jacobi solve."""
+import functools
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import box_grids
 import eigmi
 import mg_ref
 import oracle
@@ -75,6 +78,103 @@ def test_mg_solve_matches_restatement(ctx, kind, N, m):
         X = _cols(dX, n, m)
         R = ref.solve(B, cycles)
         assert np.abs(X - R).max() <= 1e-12 * np.abs(R).max(), (cycles, np.abs(X - R).max())
+    mg.close()
+    dK.close()
+
+
+def test_mg_ref_hierarchy_noncubic():
+    """CPU: the restatement on a 66 x 9 x 17 box (three distinct extents, odd and even): each
+    direction halves on its own, the coarse operators are P^T A P and bitwise symmetric."""
+    dims = (66, 9, 17)
+    for shape, values in (("p7", "const"), ("kuhn15", "edge")):
+        K = box_grids.to_scipy(box_grids.box_matrix(dims, shape, values, seed=5))
+        mg = mg_ref.Multigrid(K, dims)
+        assert [L["dims"] for L in mg.levels] == [(66, 9, 17), (33, 4, 8), (16, 2, 4)]
+        assert [L["A"].shape[0] for L in mg.levels] == [10098, 1056, 128]
+        for f, c in zip(mg.levels[:-1], mg.levels[1:]):
+            G = (f["P"].T @ f["A"] @ f["P"]).toarray()
+            assert np.abs(c["A"].toarray() - G).max() <= 1e-14 * np.abs(G).max()
+            assert (c["A"] != c["A"].T).nnz == 0
+
+
+BOX_KINDS = {"p7const": ("p7", "const", "k_boxc_mv8"), "full27const": ("full27", "const", "k_boxc_mv8"),
+             "p7edge": ("p7", "edge", "k_box_mv32")}
+
+
+@functools.lru_cache(maxsize=None)
+def _box_problem(dims, kind):
+    shape, values, _ = BOX_KINDS[kind]
+    K = box_grids.to_scipy(box_grids.box_matrix(dims, shape, values, seed=sum(dims)))
+    return K, np.random.default_rng(dims[0]).standard_normal((K.shape[0], 32))
+
+
+@functools.lru_cache(maxsize=None)
+def _box_ref(dims, kind, nu):
+    return mg_ref.Multigrid(_box_problem(dims, kind)[0], dims, nu, 5.0)
+
+
+# every grid, kind and smoother degree at least three times, both column counts on each grid
+BOX_CASES = [((130, 12, 20), "p7const", 1, 8), ((130, 12, 20), "full27const", 2, 32), ((130, 12, 20), "p7edge", 3, 32),
+             ((130, 12, 20), "p7const", 2, 32),
+             ((66, 9, 17), "p7const", 3, 32), ((66, 9, 17), "full27const", 1, 8), ((66, 9, 17), "p7edge", 2, 8),
+             ((66, 9, 17), "full27const", 3, 32),
+             ((40, 24, 10), "p7edge", 1, 32), ((40, 24, 10), "full27const", 2, 8), ((40, 24, 10), "p7const", 3, 8),
+             ((17, 40, 12), "full27const", 3, 8), ((17, 40, 12), "p7edge", 1, 8), ((17, 40, 12), "p7const", 2, 32),
+             ((17, 40, 12), "p7edge", 2, 32)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,kind,nu,m", BOX_CASES,
+                         ids=["%dx%dx%d-%s-nu%d-m%d" % (*c[0], c[1], c[2], c[3]) for c in BOX_CASES])
+def test_mg_solve_matches_restatement_boxes(ctx, dims, kind, nu, m):
+    """Grids with three distinct extents (tests/box_grids.py), so galerkin() and the transfers decode
+    (x, y, z) from extents that differ, and wide enough in x for more than one workgroup per line:
+    130 x 12 x 20 -> 65 x 6 x 10 -> 32 x 3 x 5 -> 16 x 1 x 2 prolongs in three 64-x blocks and restricts
+    into cx = 65 (three 32-x blocks) and cx = 32; fx = 66 straddles the 64-x block by two; 17 x 40 x 12
+    has y the long direction.  Smoother degrees 1 / 2 / 3 (nu != 2: the post-smoother through
+    cheb_solve + axpby).  p7edge: one value per grid edge, the fine level on the box-image kernels.
+    Bar: 1e-12 relative to max|R| against tests/mg_ref.py, whose own sensitivity to a 2.2e-16
+    perturbation of B is below 1e-15 on these grids; prints the measured deviation."""
+    K, B32 = _box_problem(dims, kind)
+    n = K.shape[0]
+    dK = _upload(ctx, K)
+    assert dK.kernel("spmm32") == BOX_KINDS[kind][2]
+    mg = eigmi.Multigrid(dK, dims, max_cols=32, smooth_degree=nu, smooth_ratio=5.0)
+    ref = _box_ref(dims, kind, nu)
+    info = mg.info()
+    assert info["levels"] == len(ref.levels) and info["coarse_rows"] == ref.levels[-1]["A"].shape[0]
+    assert info["coarse_degree"] == ref.levels[-1]["cdeg"]
+    B = np.ascontiguousarray(B32[:, :m])
+    dB, dX = _mv(ctx, B), ctx.zeros(n * m)
+    for cycles in (1, 3):
+        mg.solve(m, dB, dX, cycles)
+        X = _cols(dX, n, m)
+        R = ref.solve(B, cycles)
+        dev = np.abs(X - R).max() / np.abs(R).max()
+        print(f"multigrid {dims} {kind} nu={nu} m={m} cycles={cycles}: |X - R|.max() / |R|.max() = {dev:.2e}, "
+              f"coarse degree {info['coarse_degree']}")
+        assert np.abs(X - R).max() <= 1e-12 * np.abs(R).max(), (cycles, dev)
+    mg.close()
+    dK.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nu", [2, 3])
+def test_mg_is_symmetric_noncubic(ctx, nu):
+    """The symmetry check of test_mg_converges_and_is_symmetric on 66 x 9 x 17 at 6 iterations:
+    restriction is exactly P^T and the post-smoother the adjoint of the pre-smoother, so B^T S_6 B
+    is symmetric to rounding."""
+    dims, m = (66, 9, 17), 8
+    K, B32 = _box_problem(dims, "p7const")
+    n = K.shape[0]
+    dK = _upload(ctx, K)
+    mg = eigmi.Multigrid(dK, dims, max_cols=8, smooth_degree=nu, smooth_ratio=5.0)
+    B = np.ascontiguousarray(B32[:, :m])
+    dB, dX = _mv(ctx, B), ctx.zeros(n * m)
+    mg.solve(m, dB, dX, 6)
+    G = B.T @ _cols(dX, n, m)
+    assert np.all(np.isfinite(G))
+    assert np.abs(G - G.T).max() <= 1e-13 * np.abs(G).max(), np.abs(G - G.T).max() / np.abs(G).max()
     mg.close()
     dK.close()
 
