@@ -3,16 +3,10 @@
 //   eig_lanczos_run       the Lanczos three-term recurrence ARPACK's dsaupd runs around multMv
 //                         (arpack_geneo_wrapper.hh:257-279, :621-632) -- the benchmark unit
 //   eig_lanczos_solve     Lanczos with full DGKS re-orthogonalisation (ARPACK's conditional second pass) + Ritz extraction
-#include <algorithm>
-#include <complex>
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <string>
-#include <vector>
 
-#include "internal.h"
+#include "inverse_common.h"
 
 using namespace eigmi;
 
@@ -49,6 +43,28 @@ struct SyncEvent {
   SyncEvent &operator=(const SyncEvent &) = delete;
 };
 
+// evec[j][i] = Q(i, j): column j of the MultiVector<double,8> blocks sits at Q + (j/8)*8n + i*8 + j%8
+void copy_evecs(eig_ctx_t ctx, const double *Q, i64 n, int nev, double *evec_host)
+{
+  if (!evec_host) return;
+  const i64 m = (nev + 7) / 8 * 8;
+  std::vector<double> h((size_t)(n * m));
+  EIG_HIP(hipMemcpyAsync(h.data(), Q, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  EIG_HIP(hipStreamSynchronize(ctx->stream));
+  for (int j = 0; j < nev; ++j)
+    for (i64 i = 0; i < n; ++i) evec_host[(i64)j * n + i] = h[((j / 8) * n + i) * 8 + j % 8];
+}
+
+void random_block(eig_ctx_t ctx, i64 n, i64 m, unsigned seed, double *Q)
+{
+  std::vector<double> h((size_t)(n * m));
+  host_random_normal(n * m, seed, h.data());  // eigensolver.hh:50-55 / :137-142 / :222-227
+  EIG_HIP(hipMemcpyAsync(Q, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  EIG_HIP(hipStreamSynchronize(ctx->stream));
+}
+
+const char *const kFactorMismatch = "matmul_inverse_tallskinny_blocked: Factorization does not match size of Qout/Qin";
+
 }  // namespace
 
 // ============================================================================================
@@ -81,12 +97,7 @@ extern "C" int eig_standard_largest(eig_mat_t A, double shift, double tol, int m
     double *B[3] = {B0.d(), B1.d(), B2.d()};
     PinnedDoubles hd(2 * (size_t)m);
     SyncEvent ev[2];
-    {
-      std::vector<double> h((size_t)(n * m));
-      host_random_normal(n * m, seed, h.data());  // eigensolver.hh:50-55
-      EIG_HIP(hipMemcpyAsync(B[0], h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
-      EIG_HIP(hipStreamSynchronize(s));
-    }
+    random_block(ctx, n, m, seed, B[0]);
     if (shift != 0.0) launch_shift_diag(*A, shift, s);  // eigensolver.hh:59-66
     orthonormalize_device(ctx, n, m, B[0], EIG_ORTHO_MGS); // eigensolver.hh:69
     // :78 of iteration k recomputes A Q1, which iteration k - 1's :84 product already holds (same
@@ -138,16 +149,7 @@ extern "C" int eig_standard_largest(eig_mat_t A, double shift, double tol, int m
       if (k > 1 && dist < tol) break;
     }
     for (int j = 0; j < nev; ++j) eval_host[j] = s2[j];
-    if (evec_host)
-    {
-      // evec[j][i] = Q1(i, j): column j sits at Q1 + (j/8)*8n + i*8 + j%8 (after any look-ahead
-      // iteration on the stream, which leaves this block alone)
-      std::vector<double> h((size_t)(n * m));
-      EIG_HIP(hipMemcpyAsync(h.data(), B[basis], h.size() * 8, hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
-      for (int j = 0; j < nev; ++j)
-        for (i64 i = 0; i < n; ++i) evec_host[(i64)j * n + i] = h[((j / 8) * n + i) * 8 + j % 8];
-    }
+    copy_evecs(ctx, B[basis], n, nev, evec_host);  // (the queued look-ahead iteration leaves this block alone)
     EIG_HIP(hipStreamSynchronize(s));  // the look-ahead iteration uses this call's buffers
     mgs_lookahead_check(ctx);          // a timed-out MGS barrier: EIG_ERR_HIP, never NaN with EIG_OK
     if (iters) *iters = kk;
@@ -157,58 +159,6 @@ extern "C" int eig_standard_largest(eig_mat_t A, double shift, double tol, int m
 // ============================================================================================
 // Inverse subspace iteration with exported LU factors
 // ============================================================================================
-namespace {
-
-// The factors the inverse drivers apply: the caller's, or a host factorisation of `A` (owned).
-struct LuRef {
-  eig_lu_t lu = nullptr;
-  bool owned = false;
-  ~LuRef()
-  {
-    if (owned) eig_lu_destroy(lu);
-  }
-};
-
-void factor_host(eig_mat_s &A, const std::vector<i64> &rp, const std::vector<i32> &c, const std::vector<double> &v,
-                 LuRef &out)
-{
-  const int rc = eig_lu_create_bcsr(A.ctx, A.nb_rows, A.br, rp.data(), c.data(), v.data(), &out.lu);
-  EIG_CHECK(rc == EIG_OK, rc, std::string("LU factorisation: ") + eig_last_error(A.ctx));
-  out.owned = true;
-}
-
-void copy_evecs(eig_ctx_t ctx, const double *Q, i64 n, int nev, double *evec_host)
-{
-  if (!evec_host) return;
-  const i64 m = (nev + 7) / 8 * 8;
-  std::vector<double> h((size_t)(n * m));
-  EIG_HIP(hipMemcpyAsync(h.data(), Q, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  EIG_HIP(hipStreamSynchronize(ctx->stream));
-  for (int j = 0; j < nev; ++j)
-    for (i64 i = 0; i < n; ++i) evec_host[(i64)j * n + i] = h[((j / 8) * n + i) * 8 + j % 8];
-}
-
-void random_block(eig_ctx_t ctx, i64 n, i64 m, unsigned seed, double *Q)
-{
-  std::vector<double> h((size_t)(n * m));
-  host_random_normal(n * m, seed, h.data());  // eigensolver.hh:137-142 / :222-227
-  EIG_HIP(hipMemcpyAsync(Q, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  EIG_HIP(hipStreamSynchronize(ctx->stream));
-}
-
-// blocks: the caller runs on square blocks 1..4 (StandardInverse, the symmetric shift-invert
-// drivers); the others keep the reference's FieldMatrix<..,1,1> restriction
-void check_inverse_matrix(const eig_mat_s *A, const char *who, bool blocks = false)
-{
-  EIG_CHECK(A->br == A->bc, EIG_ERR_ARG, std::string(who) + ": blocks of input matrix must be square");
-  EIG_CHECK(blocks || A->br == 1, EIG_ERR_BLOCKSIZE,
-            "matmul_sparse_tallskinny_blocked: only implemented for FieldMatrix<..,1,1>");
-  EIG_CHECK(!distributed(*A), EIG_ERR_ARG, std::string(who) + ": single rank only");
-  EIG_CHECK(A->nb_rows == A->nb_cols, EIG_ERR_SHAPE, std::string(who) + ": square matrix required");
-}
-
-}  // namespace
-
 extern "C" int eig_standard_inverse(eig_mat_t A, eig_lu_t lu, double shift, double tol, int maxiter, int nev,
                                     unsigned seed, double *eval_host, double *evec_host, int *iters, int verbose)
 {
@@ -230,19 +180,12 @@ extern "C" int eig_standard_inverse(eig_mat_t A, eig_lu_t lu, double shift, doub
     random_block(ctx, n, m, seed, Bk[0]);
     if (shift != 0.0) launch_shift_diag(*A, shift, s);  // :145-153 (mutates A)
     LuRef F;                                           // :156 UMFPackFactorizedMatrix<ISTLM> F(A, 1)
-    if (lu)
-      F.lu = lu;
-    else
-    {
-      std::vector<i64> rp;
-      std::vector<i32> c;
-      std::vector<double> v;
+    select_factors(*A, lu, n, kFactorMismatch, F, [&] {
+      HostCsr a;
       EIG_HIP(hipStreamSynchronize(s));
-      mat_download_bcsr(*A, rp, c, v);
-      factor_host(*A, rp, c, v, F);
-    }
-    EIG_CHECK(lu_size(F.lu) == n, EIG_ERR_SHAPE,
-              "matmul_inverse_tallskinny_blocked: Factorization does not match size of Qout/Qin");
+      mat_download_bcsr(*A, a.rp, a.c, a.v);
+      return a;
+    });
     orthonormalize_device(ctx, n, m, Bk[0], EIG_ORTHO_MGS);  // :159
     auto enqueue = [&](int k) {
       double *Q = Bk[k % 2], *dp = hd.dev + (k & 1) * m;
@@ -295,33 +238,18 @@ extern "C" int eig_generalized_inverse(eig_mat_t A, eig_mat_t B, eig_lu_t lu, do
     hipStream_t s = ctx->stream;
     const i64 n = A->nb_rows;
     // copy of A, shifted (:208, :240-252): A + shift B (pattern(B) within pattern(A)) + reg I
-    std::vector<i64> rp, brp;
-    std::vector<i32> c, bc;
-    std::vector<double> v, bv;
+    HostCsr a, b;
     EIG_HIP(hipStreamSynchronize(s));
-    mat_download_bcsr(*A, rp, c, v);
-    mat_download_bcsr(*B, brp, bc, bv);
-    for (i64 i = 0; i < n; ++i)
+    mat_download_bcsr(*A, a.rp, a.c, a.v);
+    mat_download_bcsr(*B, b.rp, b.c, b.v);
+    for (i64 i = 0; i < n; ++i)  // row by row: the first row at fault decides which error is reported
     {
-      if (shift != 0.0)
-        for (i64 q = brp[i]; q < brp[i + 1]; ++q)
-        {
-          const i32 *b0 = c.data() + rp[i], *b1 = c.data() + rp[i + 1];
-          const i32 *hit = std::lower_bound(b0, b1, bc[q]);
-          EIG_CHECK(hit != b1 && *hit == bc[q], EIG_ERR_SHAPE, "GeneralizedInverse: pattern(B) must be contained in pattern(A)");
-          v[hit - c.data()] += shift * bv[q];
-        }
-      if (reg != 0.0)
-      {
-        const i32 *b0 = c.data() + rp[i], *b1 = c.data() + rp[i + 1];
-        const i32 *hit = std::lower_bound(b0, b1, (i32)i);
-        EIG_CHECK(hit != b1 && *hit == (i32)i, EIG_ERR_SHAPE, "GeneralizedInverse: A has no diagonal entry");
-        v[hit - c.data()] += reg;
-      }
+      pattern_axpy(i, i + 1, 1, a, shift, b, "GeneralizedInverse");
+      pattern_shift_diag(i, i + 1, 1, a, reg, "GeneralizedInverse");
     }
     eig_mat_t As = nullptr;
     {
-      const int rc = eig_mat_create_bcsr(ctx, n, n, 1, 1, rp.data(), c.data(), v.data(), &As);
+      const int rc = eig_mat_create_bcsr(ctx, n, n, 1, 1, a.rp.data(), a.c.data(), a.v.data(), &As);
       EIG_CHECK(rc == EIG_OK, rc, std::string("shifted copy of A: ") + eig_last_error(ctx));
     }
     struct MatGuard {
@@ -329,12 +257,7 @@ extern "C" int eig_generalized_inverse(eig_mat_t A, eig_mat_t B, eig_lu_t lu, do
       ~MatGuard() { eig_mat_destroy(m); }
     } asg{As};
     LuRef F;  // :255
-    if (lu)
-      F.lu = lu;
-    else
-      factor_host(*As, rp, c, v, F);
-    EIG_CHECK(lu_size(F.lu) == n, EIG_ERR_SHAPE,
-              "matmul_inverse_tallskinny_blocked: Factorization does not match size of Qout/Qin");
+    select_factors(*As, lu, n, kFactorMismatch, F, [&]() -> const HostCsr & { return a; });
     const i64 m = (nev / 8 + std::min(nev % 8, 1)) * 8;  // :224
     // basis ping-pong Bk[0] / Bk[1] and a scratch block Z (B Q1, then the As product): iteration i
     // reads Bk[(i - 1) % 2] and leaves its basis in Bk[i % 2], so iteration i + 1 is queued before the
@@ -380,924 +303,6 @@ extern "C" int eig_generalized_inverse(eig_mat_t A, eig_mat_t B, eig_lu_t lu, do
     EIG_HIP(hipStreamSynchronize(s));
     if (iters) *iters = iter;
     if (verbose > 0) fprintf(stdout, "GeneralizedInverse: iterations=%d relerror=%.17g\n", iter, relerror);
-  });
-}
-
-// ============================================================================================
-// computeGenSymShiftInvertMinMagnitude (arpack_geneo_wrapper.hh:581-658): thick-restart Lanczos
-// in the B-inner product on OP = (A - sigma B)^-1 B, "LM" 
-// ============================================================================================
-namespace {
-
-// Host copy of A - sigma B on A's pattern (pattern(B) within pattern(A); ashiftb.axpy(-sigma, b_),
-// arpack_geneo_wrapper.hh:599-600).
-void shifted_copy(eig_mat_s &A, eig_mat_s *B, double sigma, std::vector<i64> &rp, std::vector<i32> &c,
-                  std::vector<double> &v)
-{
-  mat_download_bcsr(A, rp, c, v);
-  if (sigma == 0.0) return;
-  // block rows; a stored block is b x b values, row-major, at v[q * bb] (b = 1: the scalar entry)
-  const i64 n = A.nb_rows;
-  const int b = A.br, bb = b * b;
-  if (!B)
-  {
-    for (i64 i = 0; i < n; ++i)
-    {
-      const i32 *b0 = c.data() + rp[i], *b1 = c.data() + rp[i + 1];
-      const i32 *hit = std::lower_bound(b0, b1, (i32)i);
-      EIG_CHECK(hit != b1 && *hit == (i32)i, EIG_ERR_SHAPE, "shift-invert: A has no diagonal entry");
-      // the identity's block: sigma off the diagonal entries of the diagonal block
-      for (int d = 0; d < b; ++d) v[(size_t)(hit - c.data()) * bb + d * b + d] -= sigma;
-    }
-    return;
-  }
-  std::vector<i64> brp;
-  std::vector<i32> bc;
-  std::vector<double> bv;
-  mat_download_bcsr(*B, brp, bc, bv);
-  for (i64 i = 0; i < n; ++i)
-    for (i64 q = brp[i]; q < brp[i + 1]; ++q)
-    {
-      const i32 *b0 = c.data() + rp[i], *b1 = c.data() + rp[i + 1];
-      const i32 *hit = std::lower_bound(b0, b1, bc[q]);
-      EIG_CHECK(hit != b1 && *hit == bc[q], EIG_ERR_SHAPE, "shift-invert: pattern(B) must be contained in pattern(A)");
-      for (int t = 0; t < bb; ++t) v[(size_t)(hit - c.data()) * bb + t] -= sigma * bv[(size_t)q * bb + t];
-    }
-}
-
-}  // namespace
-
-namespace {
-
-// blocks: square blocks 1..4 (the symmetric driver, like the reference's, needs only mv and the
-// factorisation); B then has A's block size
-void shift_invert_check(eig_mat_t A, eig_mat_t B, bool blocks = false)
-{
-  check_inverse_matrix(A, "computeGenSymShiftInvertMinMagnitude", blocks);
-  if (B)
-  {
-    check_inverse_matrix(B, "computeGenSymShiftInvertMinMagnitude", blocks);
-    EIG_CHECK(B->br == A->br, EIG_ERR_BLOCKSIZE, "shift-invert: A and B block sizes differ");
-    EIG_CHECK(B->ctx == A->ctx && B->nb_rows == A->nb_rows, EIG_ERR_SHAPE, "shift-invert: A and B sizes differ");
-  }
-}
-
-// The factorisation of A - sigma B (arpack_geneo_wrapper.hh:597-601): the caller's, or a host one.
-void shift_invert_factor(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma, LuRef &F)
-{
-  if (lu)
-    F.lu = lu;
-  else
-  {
-    std::vector<i64> rp;
-    std::vector<i32> c;
-    std::vector<double> v;
-    EIG_HIP(hipStreamSynchronize(A->ctx->stream));
-    shifted_copy(*A, B, sigma, rp, c, v);
-    factor_host(*A, rp, c, v, F);
-  }
-  EIG_CHECK(lu_size(F.lu) == A->nb_rows * A->br, EIG_ERR_SHAPE, "shift-invert: factorisation size differs from A");
-}
-
-// One computeGenSymShiftInvertMinMagnitude solve (ARSymGenEig 'S' mode, "LM") with the factors F.
-void shift_invert_core(eig_mat_t A, eig_mat_t B, const LuRef &F, double sigma, int nev, int ncv, double tol, int maxit,
-                       unsigned seed, double *eval_host, double *evec_host, int *restarts)
-{
-    eig_ctx_t ctx = A->ctx;
-    EIG_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const i64 n = A->nb_rows * A->br;  // scalar rows (square blocks 1..4: only mv and the factors are used)
-    if (ncv <= 0) ncv = (int)std::min<i64>(n, std::max(2 * nev + 1, 20));  // ARPACK++ ncv = 0 (auto)
-    EIG_CHECK(nev < ncv && ncv <= n && ncv <= 500, EIG_ERR_ARG, "shift-invert: need nev < ncv <= min(n, 500)");
-    if (tol <= 0.0) tol = 2.220446049250313e-16;  // tol = 0: machine precision (ARPACK)
-    if (maxit <= 0) maxit = 100 * nev;            // maxit = 0: 100 nev (ARPACK++)
-    const int m = ncv;
-    // basis V and BV (= B V; V itself when B is NULL), column-major, m + 1 vectors each
-    DevBuf Vb((size_t)(m + 1) * n * 8), BVb(B ? (size_t)(m + 1) * n * 8 : 8), Wb(n * 8), BWb(n * 8), X8b(n * 64),
-        Y8b(n * 64), Tb((size_t)2 * (m + 1) * n * 8), cb((size_t)(m + 8) * 8 * 2);
-    double *V = Vb.d(), *BV = B ? BVb.d() : Vb.d(), *W = Wb.d(), *BW = BWb.d(), *X8 = X8b.d(), *Y8 = Y8b.d();
-    double *cd = cb.d(), *sc = cd + m + 8;
-    EIG_HIP(hipMemsetAsync(X8, 0, n * 64, s));
-    auto bmul = [&](double *x, double *y) {  // y = B x
-      if (B) launch_spmv(*B, x, y, nullptr, 0, B->nslices, s);
-      else if (y != x) EIG_HIP(hipMemcpyAsync(y, x, n * 8, hipMemcpyDeviceToDevice, s));
-    };
-    auto dot = [&](const double *x, const double *y) {
-      launch_dot(n, x, y, sc, 0, s, ctx->red);
-      double h = 0.0;
-      EIG_HIP(hipMemcpyAsync(&h, sc, 8, hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
-      return h;
-    };
-    auto op = [&](const double *bx, double *y) {  // y = (A - sigma B)^-1 bx (column 0 of the 8-wide solve)
-      EIG_HIP(hipMemcpy2DAsync(X8, 64, bx, 8, 8, n, hipMemcpyDeviceToDevice, s));
-      lu_inverse_device(F.lu, 8, X8, Y8, s);
-      EIG_HIP(hipMemcpy2DAsync(y, 8, Y8, 64, 8, n, hipMemcpyDeviceToDevice, s));
-    };
-    // start vector: mt19937(seed) normal numbers put into the range of OP (as ARPACK's dgetv0 does
-    // for the generalised modes, so a singular B cannot leave null(B) components in the basis),
-    // B-normalised
-    {
-      std::vector<double> h(n);
-      host_random_normal(n, seed, h.data());
-      EIG_HIP(hipMemcpyAsync(W, h.data(), n * 8, hipMemcpyHostToDevice, s));
-      bmul(W, BW);
-      op(BW, V);
-      bmul(V, BV);
-      const double nb = std::sqrt(dot(V, BV));
-      launch_scal(n, 1.0 / nb, V, s);
-      if (B) launch_scal(n, 1.0 / nb, BV, s);
-    }
-    std::vector<double> T((size_t)m * m, 0.0), ctot(m + 1), th, Y;
-    // per step j of an extension: the two CGS passes' coefficients (m + 1 each) and (w, B w), kept on
-    // the device and read back once per extension -- the steps queue without a host round trip (the
-    // host sums and scalars are those the step-by-step loop computed; a breakdown is reported after
-    // the extension, with the same error)
-    const i64 cstride = 2 * (i64)(m + 1) + 1;
-    DevBuf coefb((size_t)m * cstride * 8);
-    double *coef = coefb.d();
-    std::vector<double> coefh((size_t)m * cstride);
-    int k = 0, nrestart = 0;
-    double betam = 0.0;
-    std::vector<int> want;
-    bool done = false;
-    while (!done)
-    {
-      // extend the Lanczos factorisation from k to m vectors
-      for (int j = k; j < m; ++j)
-      {
-        double *bvj = BV + (i64)j * n;
-        double *cj = coef + (i64)j * cstride;
-        // w = (A - sigma B)^-1 (B v_j): the reverse-communication product of ARSymGenEig 'S' mode
-        op(bvj, W);
-        for (int pass = 0; pass < 2; ++pass)  // DGKS / CGS2 against v_0 .. v_j in the B-inner product
-        {
-          launch_gemv_t(n, j + 1, BV, n, W, cj + pass * (m + 1), 0, s, ctx->red);
-          launch_gemv_n_sub(n, j + 1, V, n, cj + pass * (m + 1), nullptr, W, s);
-        }
-        bmul(W, BW);
-        launch_dot(n, W, BW, cj + 2 * (m + 1), 0, s, ctx->red);  // beta_j^2
-        double *vn = V + (i64)(j + 1) * n, *bvn = BV + (i64)(j + 1) * n;
-        EIG_HIP(hipMemcpyAsync(vn, W, n * 8, hipMemcpyDeviceToDevice, s));
-        launch_scal_dev(n, cj + 2 * (m + 1), true, vn, s);  // 1 / sqrt(beta_j^2)
-        if (B)
-        {
-          EIG_HIP(hipMemcpyAsync(bvn, BW, n * 8, hipMemcpyDeviceToDevice, s));
-          launch_scal_dev(n, cj + 2 * (m + 1), true, bvn, s);
-        }
-      }
-      EIG_HIP(hipMemcpyAsync(coefh.data() + (size_t)k * cstride, coef + (i64)k * cstride,
-                             (size_t)(m - k) * cstride * 8, hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
-      for (int j = k; j < m; ++j)
-      {
-        const double *ch = coefh.data() + (size_t)j * cstride;
-        std::fill(ctot.begin(), ctot.end(), 0.0);
-        for (int pass = 0; pass < 2; ++pass)
-          for (int i = 0; i <= j; ++i) ctot[i] += ch[pass * (m + 1) + i];
-        for (int i = 0; i <= j; ++i) T[(size_t)i * m + j] = T[(size_t)j * m + i] = ctot[i];
-        const double beta = std::sqrt(std::max(0.0, ch[2 * (m + 1)]));
-        double tn = 0.0;
-        for (int i = 0; i <= j; ++i) tn = std::max(tn, std::fabs(ctot[i]));
-        EIG_CHECK(beta > 1e-14 * tn, EIG_ERR_BREAKDOWN,
-                  "shift-invert Lanczos: invariant subspace reached (choose ncv < n or another seed)");
-        if (j + 1 < m) T[(size_t)(j + 1) * m + j] = T[(size_t)j * m + (j + 1)] = beta;
-        betam = beta;
-      }
-      sym_eig(m, T, th, Y);
-      // "LM" on OP: the nev Ritz values of largest magnitude (eigenvalues of the pencil nearest sigma)
-      std::vector<int> ord(m);
-      std::iota(ord.begin(), ord.end(), 0);
-      std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return std::fabs(th[a]) > std::fabs(th[b]); });
-      want.assign(ord.begin(), ord.begin() + nev);
-      bool conv = true;
-      for (int i : want)
-        if (std::fabs(betam * Y[(size_t)(m - 1) * m + i]) > tol * std::fabs(th[i])) conv = false;
-      if (conv || nrestart >= maxit)
-      {
-        done = true;
-        break;
-      }
-      // thick restart: keep kk Ritz vectors of largest |theta|, then the residual vector
-      const int kk = std::min(m - 2, nev + (m - nev) / 2);
-      std::vector<double> coef(m);
-      double *Tmp = Tb.d();
-      for (int q = 0; q < kk; ++q)
-      {
-        for (int i = 0; i < m; ++i) coef[i] = Y[(size_t)i * m + ord[q]];
-        EIG_HIP(hipMemcpyAsync(cd, coef.data(), m * 8, hipMemcpyHostToDevice, s));
-        launch_gemv_n_set(n, m, V, n, cd, nullptr, Tmp + (i64)q * n, s);
-        if (B) launch_gemv_n_set(n, m, BV, n, cd, nullptr, Tmp + (i64)(kk + q) * n, s);
-        EIG_HIP(hipStreamSynchronize(s));
-      }
-      EIG_HIP(hipMemcpyAsync(V, Tmp, (size_t)kk * n * 8, hipMemcpyDeviceToDevice, s));
-      EIG_HIP(hipMemcpyAsync(V + (i64)kk * n, V + (i64)m * n, n * 8, hipMemcpyDeviceToDevice, s));
-      if (B)
-      {
-        EIG_HIP(hipMemcpyAsync(BV, Tmp + (i64)kk * n, (size_t)kk * n * 8, hipMemcpyDeviceToDevice, s));
-        EIG_HIP(hipMemcpyAsync(BV + (i64)kk * n, BV + (i64)m * n, n * 8, hipMemcpyDeviceToDevice, s));
-      }
-      std::fill(T.begin(), T.end(), 0.0);
-      for (int q = 0; q < kk; ++q) T[(size_t)q * m + q] = th[ord[q]];
-      k = kk;
-      ++nrestart;
-    }
-    // eigenpairs of the pencil: lambda = sigma + 1 / theta, sorted ascending (:636-648)
-    std::vector<int> idx(nev);
-    std::iota(idx.begin(), idx.end(), 0);
-    std::vector<double> lam(nev);
-    for (int i = 0; i < nev; ++i) lam[i] = sigma + 1.0 / th[want[i]];
-    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return lam[a] < lam[b]; });
-    for (int i = 0; i < nev; ++i) eval_host[i] = lam[idx[i]];
-    if (evec_host)
-    {
-      // purified Ritz vectors (ARPACK dseupd for the spectral-transformation modes): x = OP(V y) /
-      // theta = V y + (beta_m y_m / theta) v_m.  B = I: that linear combination.  Generalised: the
-      // operator applied explicitly to B V y = BV y, x = (A - sigma B)^-1 (BV y) / theta, then
-      // B-normalised -- with a singular B (the harness's partition-of-unity B) the basis picks up
-      // null(B) components through the projections that the B-inner products never see and that
-      // grow over thick restarts; OP maps into range(OP), where they cannot live.
-      std::vector<double> coef(m + 1);
-      for (int q = 0; q < nev; ++q)
-      {
-        const int col = want[idx[q]];
-        for (int i = 0; i < m; ++i) coef[i] = Y[(size_t)i * m + col];
-        coef[m] = betam * Y[(size_t)(m - 1) * m + col] / th[col];
-        EIG_HIP(hipMemcpyAsync(cd, coef.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
-        if (!B)
-          launch_gemv_n_set(n, m + 1, V, n, cd, nullptr, W, s);
-        else
-        {
-          launch_gemv_n_set(n, m, BV, n, cd, nullptr, BW, s);
-          op(BW, W);
-          bmul(W, BW);
-          const double xb = dot(W, BW);
-          EIG_CHECK(xb > 0.0, EIG_ERR_BREAKDOWN, "shift-invert: purified Ritz vector has no B-norm");
-          launch_scal(n, 1.0 / std::sqrt(xb), W, s);
-        }
-        EIG_HIP(hipMemcpyAsync(evec_host + (i64)q * n, W, n * 8, hipMemcpyDeviceToHost, s));
-        EIG_HIP(hipStreamSynchronize(s));
-      }
-    }
-    if (restarts) *restarts = nrestart;
-}
-
-// Block variant (EIG_SI_BLOCK, the default where the basis fits): the same OP, the same wanted
-// pairs and the same B-inner product, by block Lanczos with Krylov-Schur (thick) restarts on p
-// columns at once.  Why: one application of OP is the block-inverse triangular solve, a chain over
-// the factor's 64-row blocks that one workgroup walks per 8 columns -- latency-bound, so p = 16
-// columns cost what one column costs (two chains side by side), and a block Krylov space reaches
-// the wanted pairs in a fraction of the applications the one-vector recurrence needs (nev = 8 on
-// the 200^2 GenEO pencil: 44 applications -> 8).  Basis V (c columns, MultiVector<double,8>
-// blocks) and BV = B V; per block step, with V_a the last p columns:
-//     W = OP(B V_a);  H = (B V)^T W, W -= V H  (twice: CGS2 in the B-inner product);
-//     W = F R (CholQR2 in the B-inner product);  T(:, a) = H, T(next, a) = R.
-// Rayleigh-Ritz on T; the residual of Ritz pair i is ||R y_i(a)|| (V_next is B-orthonormal), so the
-// convergence test is ||R y_i(a)|| <= tol |theta_i|.  Restart: U = V Y(:, kept) (kk Ritz vectors of
-// largest |theta|), T = diag(theta_kept) coupled to F by C = R Y(a, kept) -- again a block Krylov
-// decomposition OP [U F] = [U F] T + ..., extended from F.  Eigenvectors purified like the one-vector
-// path: x = OP(B V y) / theta, B-normalised (one block solve for all of them).
-struct SiBlockShape {
-  int nw, p, kk, cmax;
-};
-
-SiBlockShape si_block_shape(int nev, int ncv)
-{
-  SiBlockShape g;
-  g.nw = (nev + 7) / 8 * 8;
-  g.p = std::max(16, g.nw);
-  g.kk = std::max((nev + (nev + 1) / 2 + 7) / 8 * 8, 3 * g.p);
-  g.cmax = std::max(g.kk + 3 * g.p, (ncv + 7) / 8 * 8);
-  return g;
-}
-
-// the block method's reductions within the context's tickets: the projection Gram (cmax x p, partials
-// in a buffer sized for the launch), the CholQR Gram (p x p) and the purified vectors' B-norms
-// (the projection Gram goes in row slices of 64 when it is larger: see gram_rows)
-bool si_block_fits(const SiBlockShape &g)
-{
-  return gram_mv8_chunks(64, g.p) <= kNumTickets && gram_mv8_chunks(g.p, g.p) <= kNumTickets &&
-         g.nw / 8 <= kNumTickets;
-}
-
-// H (c x p, row i at H + i p) = Q1(:, 0 .. c)^T Q2: one launch where its output chunks fit the
-// tickets, else row slices (each a multiple of 64 rows) in stream order
-void gram_rows(eig_ctx_t ctx, i64 n, int c, int p, const double *Q1, const double *Q2, double *H, hipStream_t s)
-{
-  int rc = c;
-  while (gram_mv8_chunks(rc, p) > kNumTickets) rc = std::max(64, (rc / 2 + 63) / 64 * 64);
-  for (int r0 = 0; r0 < c; r0 += rc)
-    launch_gram_panel(ctx, n, n, std::min(rc, c - r0), p, Q1 + (i64)r0 * n, Q2, H + (size_t)r0 * p, s);
-}
-
-void shift_invert_block_core(eig_mat_t A, eig_mat_t B, const LuRef &F, double sigma, int nev, int ncv, double tol,
-                             int maxit, unsigned seed, double *eval_host, double *evec_host, int *restarts)
-{
-  eig_ctx_t ctx = A->ctx;
-  EIG_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const i64 n = A->nb_rows;
-  const SiBlockShape g = si_block_shape(nev, ncv);
-  const int p = g.p, kk = g.kk, cmax = g.cmax, cap = cmax + p;
-  EIG_CHECK(nev < n && cap <= n, EIG_ERR_ARG, "shift-invert (block): the block basis does not fit n");
-  EIG_CHECK(si_block_fits(g), EIG_ERR_ARG, "shift-invert (block): nev too large for the block method (use EIG_SI_SINGLE)");
-  if (tol <= 0.0) tol = 2.220446049250313e-16;
-  if (maxit <= 0) maxit = 100 * nev;
-  const int wk = std::max(kk, g.nw);
-  DevBuf Vb((size_t)cap * n * 8), BVb(B ? (size_t)cap * n * 8 : 8), W1b((size_t)p * n * 8), W2b((size_t)p * n * 8),
-      BWb((size_t)p * n * 8), Ub((size_t)wk * n * 8), Hb((size_t)cap * std::max(p, wk) * 8);
-  double *V = Vb.d(), *BV = B ? BVb.d() : V, *W = W1b.d(), *Wt = W2b.d(), *BW = BWb.d(), *U = Ub.d(), *dH = Hb.d();
-  auto bmul = [&](const double *x, double *y, int cols) {  // y = B x (cols columns)
-    if (B) launch_spmm_mv8(*B, cols, x, y, s);
-    else if (y != x) EIG_HIP(hipMemcpyAsync(y, x, (size_t)cols * n * 8, hipMemcpyDeviceToDevice, s));
-  };
-  // y (q columns) = x (px columns) M, M px x q row-major on the host
-  std::vector<double> mneg;
-  auto mul_small = [&](const double *x, int px, const std::vector<double> &M, int q, double *y) {
-    mneg.resize((size_t)px * q);
-    for (size_t k = 0; k < mneg.size(); ++k) mneg[k] = -M[k];
-    EIG_HIP(hipMemcpyAsync(dH, mneg.data(), mneg.size() * 8, hipMemcpyHostToDevice, s));
-    EIG_HIP(hipMemsetAsync(y, 0, (size_t)q * n * 8, s));
-    for (int i = 0; i < px / 8; ++i) launch_project(n, q, x + (i64)i * 8 * n, y, dH + (size_t)i * 8 * q, s);
-    EIG_HIP(hipStreamSynchronize(s));  // (mneg is reused by the next call)
-  };
-  // OP on p columns: y = (A - sigma B)^-1 bx (bx is consumed as the solve's scratch)
-  auto op = [&](double *bx, double *y, int cols) { lu_inverse_device(F.lu, cols, bx, y, s); };
-  // W (p columns, scratch Wt) -> B-orthonormal F at dst / bdst with W = F R; false on a rank loss
-  std::vector<double> G((size_t)p * p), R((size_t)p * p), Ri((size_t)p * p), Rtot((size_t)p * p);
-  auto bortho = [&](double *dst, double *bdst) -> bool {
-    std::fill(Rtot.begin(), Rtot.end(), 0.0);
-    for (int i = 0; i < p; ++i) Rtot[(size_t)i * p + i] = 1.0;
-    for (int pass = 0; pass < 2; ++pass)
-    {
-      double *bw = B ? BW : W;
-      bmul(W, bw, p);
-      launch_gram_panel(ctx, n, n, p, p, W, bw, dH, s);
-      EIG_HIP(hipMemcpyAsync(G.data(), dH, G.size() * 8, hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
-      for (int i = 0; i < p; ++i)
-        for (int j = i + 1; j < p; ++j) G[(size_t)j * p + i] = G[(size_t)i * p + j];
-      if (!chol_upper(p, G.data(), R.data())) return false;
-      tri_upper_inv(p, R.data(), Ri.data());
-      mul_small(W, p, Ri, p, Wt);
-      std::swap(W, Wt);
-      std::vector<double> Rn((size_t)p * p, 0.0);  // Rtot = R Rtot
-      for (int i = 0; i < p; ++i)
-        for (int k = i; k < p; ++k)
-          for (int j = k; j < p; ++j) Rn[(size_t)i * p + j] += R[(size_t)i * p + k] * Rtot[(size_t)k * p + j];
-      Rtot.swap(Rn);
-    }
-    EIG_HIP(hipMemcpyAsync(dst, W, (size_t)p * n * 8, hipMemcpyDeviceToDevice, s));
-    bmul(dst, bdst, p);
-    return true;
-  };
-  // start block: normal numbers put into the range of OP (dgetv0 for the generalised modes), then
-  // B-orthonormalised
-  {
-    launch_fill_normal((i64)p * n, seed, Wt, s);
-    bmul(Wt, BW, p);
-    op(BW, W, p);
-    EIG_CHECK(bortho(V, BV), EIG_ERR_BREAKDOWN, "shift-invert (block): start block is rank deficient");
-  }
-  std::vector<double> T((size_t)cap * cap, 0.0), th, Y, Hh, Ht, Tc;
-  int c = p, nrestart = 0;
-  std::vector<int> ord;
-  for (;;)
-  {
-    // apply OP to the active block V(:, a .. c), project, B-orthonormalise: F = V(:, c .. c + p)
-    const int a = c - p;
-    EIG_HIP(hipMemcpyAsync(BW, BV + (i64)a * n, (size_t)p * n * 8, hipMemcpyDeviceToDevice, s));
-    op(BW, W, p);
-    Ht.assign((size_t)c * p, 0.0);
-    for (int pass = 0; pass < 2; ++pass)  // CGS2 against V(:, 0 .. c) in the B-inner product
-    {
-      gram_rows(ctx, n, c, p, BV, W, dH, s);
-      for (int i = 0; i < c / 8; ++i) launch_project(n, p, V + (i64)i * 8 * n, W, dH + (size_t)i * 8 * p, s);
-      Hh.resize((size_t)c * p);
-      EIG_HIP(hipMemcpyAsync(Hh.data(), dH, Hh.size() * 8, hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
-      for (size_t k = 0; k < Hh.size(); ++k) Ht[k] += Hh[k];
-    }
-    for (int i = 0; i < c; ++i)
-      for (int j = 0; j < p; ++j) T[(size_t)i * cap + a + j] = T[(size_t)(a + j) * cap + i] = Ht[(size_t)i * p + j];
-    EIG_CHECK(bortho(V + (i64)c * n, BV + (i64)c * n), EIG_ERR_BREAKDOWN,
-              "shift-invert (block): invariant subspace reached (choose another seed or the one-vector solver)");
-    // Rayleigh-Ritz on the c columns: at the end of the first cycle, then after every application
-    // (stop as soon as the wanted pairs converged).  Inside the first cycle the wanted pairs have not
-    // converged in any run seen, and the host eigen-solve of T costs O(c^3) (~1-2 ms at c = 64-96).
-    if (nrestart == 0 && c + p <= cmax)
-    {
-      for (int i = 0; i < p; ++i)
-        for (int j = 0; j < p; ++j)
-          T[(size_t)(c + i) * cap + a + j] = T[(size_t)(a + j) * cap + c + i] = Rtot[(size_t)i * p + j];
-      c += p;
-      continue;
-    }
-    Tc.resize((size_t)c * c);
-    for (int i = 0; i < c; ++i)
-      for (int j = 0; j < c; ++j) Tc[(size_t)i * c + j] = T[(size_t)i * cap + j];
-    sym_eig(c, Tc, th, Y);  // Y[i * c + j]: component i of Ritz vector j
-    // "LM" on OP: the Ritz values of largest magnitude (eigenvalues of the pencil nearest sigma)
-    ord.resize(c);
-    std::iota(ord.begin(), ord.end(), 0);
-    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return std::fabs(th[x]) > std::fabs(th[y]); });
-    // coupling of the Ritz vectors to F: C(:, j) = R y_j(a .. a + p)
-    auto coupling = [&](int j, int i) {
-      double v = 0.0;
-      for (int k = i; k < p; ++k) v += Rtot[(size_t)i * p + k] * Y[(size_t)(a + k) * c + j];
-      return v;
-    };
-    bool conv = c >= std::min(nev + 1, cmax);
-    for (int q = 0; q < nev && conv; ++q)
-    {
-      double r2 = 0.0;
-      for (int i = 0; i < p; ++i)
-      {
-        const double v = coupling(ord[q], i);
-        r2 += v * v;
-      }
-      if (std::sqrt(r2) > tol * std::fabs(th[ord[q]])) conv = false;
-    }
-    if (conv) break;
-    if (c + p <= cmax)
-    {
-      // F joins the basis: T(c .. c + p, a .. c) = R
-      for (int i = 0; i < p; ++i)
-        for (int j = 0; j < p; ++j)
-          T[(size_t)(c + i) * cap + a + j] = T[(size_t)(a + j) * cap + c + i] = Rtot[(size_t)i * p + j];
-      c += p;
-      continue;
-    }
-    if (nrestart >= maxit) break;
-    // thick restart: U = V Y(:, kept), F moves behind it, T = diag(theta_kept) + the coupling C
-    {
-      std::vector<double> Ysel((size_t)c * kk);
-      for (int r = 0; r < c; ++r)
-        for (int q = 0; q < kk; ++q) Ysel[(size_t)r * kk + q] = Y[(size_t)r * c + ord[q]];
-      mul_small(V, c, Ysel, kk, U);
-      EIG_HIP(hipMemcpyAsync(V, U, (size_t)kk * n * 8, hipMemcpyDeviceToDevice, s));
-      EIG_HIP(hipMemcpyAsync(V + (i64)kk * n, V + (i64)c * n, (size_t)p * n * 8, hipMemcpyDeviceToDevice, s));
-      if (B)
-      {
-        EIG_HIP(hipMemcpyAsync(BV + (i64)kk * n, BV + (i64)c * n, (size_t)p * n * 8, hipMemcpyDeviceToDevice, s));
-        bmul(V, BV, kk);
-      }
-      std::fill(T.begin(), T.end(), 0.0);
-      for (int q = 0; q < kk; ++q)
-      {
-        T[(size_t)q * cap + q] = th[ord[q]];
-        for (int i = 0; i < p; ++i) T[(size_t)(kk + i) * cap + q] = T[(size_t)q * cap + kk + i] = coupling(ord[q], i);
-      }
-      c = kk + p;
-      ++nrestart;
-    }
-  }
-  // eigenpairs of the pencil: lambda = sigma + 1 / theta, ascending (:636-648)
-  std::vector<int> idx(nev);
-  std::iota(idx.begin(), idx.end(), 0);
-  std::vector<double> lam(nev);
-  for (int q = 0; q < nev; ++q) lam[q] = sigma + 1.0 / th[ord[q]];
-  std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return lam[x] < lam[y]; });
-  for (int q = 0; q < nev; ++q) eval_host[q] = lam[idx[q]];
-  if (evec_host)
-  {
-    const int nw = g.nw;
-    std::vector<double> Ysel((size_t)c * nw, 0.0);
-    for (int q = 0; q < nev; ++q)
-    {
-      const int j = ord[idx[q]];
-      for (int r = 0; r < c; ++r) Ysel[(size_t)r * nw + q] = Y[(size_t)r * c + j] / th[j];
-    }
-    mul_small(BV, c, Ysel, nw, U);  // B V y / theta
-    op(U, W, nw);                   // x = OP(B V y) / theta
-    double *bw = B ? BW : W;
-    bmul(W, bw, nw);
-    launch_dot_diag_mv8(n, nw, W, bw, dH, 0, s, ctx->red);
-    std::vector<double> xb(nw), h((size_t)nw * n);
-    EIG_HIP(hipMemcpyAsync(xb.data(), dH, nw * 8, hipMemcpyDeviceToHost, s));
-    EIG_HIP(hipMemcpyAsync(h.data(), W, h.size() * 8, hipMemcpyDeviceToHost, s));
-    EIG_HIP(hipStreamSynchronize(s));
-    for (int q = 0; q < nev; ++q)
-    {
-      EIG_CHECK(xb[q] > 0.0, EIG_ERR_BREAKDOWN, "shift-invert: purified Ritz vector has no B-norm");
-      const double sc = 1.0 / std::sqrt(xb[q]);
-      for (i64 i = 0; i < n; ++i) evec_host[(i64)q * n + i] = sc * h[((i64)(q / 8) * n + i) * 8 + q % 8];
-    }
-  }
-  if (restarts) *restarts = nrestart;
-}
-
-// EIG_SI_AUTO: the block solver where its basis (cmax + p columns) is at most a quarter of n
-bool si_use_block(i64 n, int nev, int ncv, int flags)
-{
-  if (flags & EIG_SI_SINGLE) return false;
-  if (flags & EIG_SI_BLOCK) return true;
-  const SiBlockShape g = si_block_shape(nev, ncv);
-  // the basis within n / 4, and the reductions within the tickets
-  return (i64)(g.cmax + g.p) * 4 <= n && si_block_fits(g);
-}
-
-void shift_invert_run(eig_mat_t A, eig_mat_t B, const LuRef &F, double sigma, int nev, int ncv, double tol, int maxit,
-                      unsigned seed, double *eval_host, double *evec_host, int *restarts, int flags)
-{
-  if (A->br > 1)
-  {
-    // blocked matrices: the one-vector method (mv and the factors only); the block method's panel
-    // kernels are FieldMatrix<..,1,1> code
-    EIG_CHECK(!(flags & EIG_SI_BLOCK), EIG_ERR_BLOCKSIZE,
-              "shift-invert (block): only implemented for FieldMatrix<..,1,1> (use EIG_SI_AUTO / EIG_SI_SINGLE)");
-    shift_invert_core(A, B, F, sigma, nev, ncv, tol, maxit, seed, eval_host, evec_host, restarts);
-    return;
-  }
-  if (si_use_block(A->nb_rows, nev, ncv, flags))
-    shift_invert_block_core(A, B, F, sigma, nev, ncv, tol, maxit, seed, eval_host, evec_host, restarts);
-  else
-    shift_invert_core(A, B, F, sigma, nev, ncv, tol, maxit, seed, eval_host, evec_host, restarts);
-}
-
-}  // namespace
-
-extern "C" int eig_shift_invert_solve_ex(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma, int nev, int ncv,
-                                         double tol, int maxit, unsigned seed, double *eval_host, double *evec_host,
-                                         int *restarts, int flags)
-{
-  return guard(A ? A->ctx : nullptr, [&] {
-    EIG_CHECK(A && eval_host && nev > 0, EIG_ERR_ARG, "eig_shift_invert_solve: bad argument");
-    EIG_CHECK((flags & ~(EIG_SI_SINGLE | EIG_SI_BLOCK)) == 0 && flags != (EIG_SI_SINGLE | EIG_SI_BLOCK), EIG_ERR_ARG,
-              "eig_shift_invert_solve_ex: unknown flags");
-    shift_invert_check(A, B, true);
-    EIG_CHECK(A->br == 1 || !(flags & EIG_SI_BLOCK), EIG_ERR_BLOCKSIZE,
-              "shift-invert (block): only implemented for FieldMatrix<..,1,1> (use EIG_SI_AUTO / EIG_SI_SINGLE)");
-    EIG_HIP(hipSetDevice(A->ctx->device));
-    LuRef F;
-    shift_invert_factor(A, B, lu, sigma, F);
-    shift_invert_run(A, B, F, sigma, nev, ncv, tol, maxit, seed, eval_host, evec_host, restarts, flags);
-  });
-}
-
-extern "C" int eig_shift_invert_solve(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma, int nev, int ncv,
-                                      double tol, int maxit, unsigned seed, double *eval_host, double *evec_host,
-                                      int *restarts)
-{
-  return eig_shift_invert_solve_ex(A, B, lu, sigma, nev, ncv, tol, maxit, seed, eval_host, evec_host, restarts,
-                                   EIG_SI_AUTO);
-}
-
-// computeGenSymShiftInvertMinMagnitudeAdaptive (arpack_geneo_wrapper.hh:661-774): solve with nev =
-// initial_nev; while the largest returned eigenvalue is below `threshold` and nev < max_nev, grow
-// nev to min(max_nev, int(nev * 1.3)) (:770; the comment at :665 says 50 %, the code 1.3) and solve
-// again from the same start (ARPACK++'s default initial guess each pass).  One factorisation of
-// A - sigma B serves every pass.  ncv = 0 (auto) and maxit = nIterationsMax_ * nev as the reference.
-extern "C" int eig_shift_invert_adaptive(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma, double threshold,
-                                         int initial_nev, int max_nev, double tol, int maxit_per_nev, unsigned seed,
-                                         double *eval_host, double *evec_host, int *nev_out, int *passes)
-{
-  return guard(A ? A->ctx : nullptr, [&] {
-    EIG_CHECK(A && eval_host && nev_out && initial_nev > 0 && max_nev > 0, EIG_ERR_ARG,
-              "eig_shift_invert_adaptive: bad argument");
-    // (arpack_geneo_wrapper.hh:693-694: "initial_nev too large")
-    EIG_CHECK(initial_nev <= max_nev, EIG_ERR_ARG, "eig_shift_invert_adaptive: initial_nev too large");
-    shift_invert_check(A, B, true);
-    EIG_HIP(hipSetDevice(A->ctx->device));
-    LuRef F;
-    shift_invert_factor(A, B, lu, sigma, F);
-    int nev = initial_nev, pass = 0;
-    for (;;)
-    {
-      const int maxit = maxit_per_nev > 0 ? maxit_per_nev * nev : 0;
-      shift_invert_run(A, B, F, sigma, nev, 0, tol, maxit, seed, eval_host, evec_host, nullptr, EIG_SI_AUTO);
-      ++pass;
-      if (eval_host[nev - 1] >= threshold || nev >= max_nev) break;
-      // (:770; for nev <= 3, int(nev * 1.3) == nev and the reference would solve the same problem
-      // forever -- there nev grows by one instead; from nev = 4 on the sequences are identical)
-      nev = std::min(max_nev, std::max(nev + 1, (int)(nev * 1.3)));
-    }
-    *nev_out = nev;
-    if (passes) *passes = pass;
-  });
-}
-
-// ============================================================================================
-// Non-symmetric modes (arpack_geneo_wrapper.hh:428-578): computeStdNonSymMinMagnitude
-// (ARNonSymStdEig on OP = (A - sigma B)^-1 B, "LM", lambda = sigma + 1 / Re(nu)) and
-// computeGenNonSymShiftInvertMinMagnitude (ARNonSymGenEig, real shift-invert mode: the same OP in
-// the B-inner product, lambda = sigma + 1 / nu).  ARPACK's dnaupd restarts implicitly with exact
-// shifts; here the restart is Stewart's Krylov-Schur in its eigenvector-basis form: the projected
-// matrix G of the Krylov decomposition  OP V = V G + f c^T  has its wanted eigenvectors (real and
-// imaginary parts of complex pairs) orthonormalised into Z (m x kk); span(Z) is G-invariant, so
-// OP (V Z) = (V Z)(Z^T G Z) + f (Z^T c)^T is again a Krylov decomposition, extended by Arnoldi
-// steps (CGS2 in the chosen inner product) back to m vectors.  The same wanted Ritz values as
-// ARPACK's restart filter (the polynomial with the unwanted Ritz values as roots annihilates the
-// complement of span(Z)); convergence: ||f|| |c^T y| <= tol |nu| (dnaupd's Ritz estimate).
-// ============================================================================================
-namespace {
-
-void arnoldi_core(eig_mat_t A, eig_mat_t B, const LuRef &F, double sigma, int nev, int ncv, double tol, int maxit,
-                  unsigned seed, bool gen, double *eval_re, double *eval_im, double *evec_host, int *restarts)
-{
-  typedef std::complex<double> C;
-  eig_ctx_t ctx = A->ctx;
-  EIG_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const i64 n = A->nb_rows;
-  if (ncv <= 0) ncv = (int)std::min<i64>(n, std::max(2 * nev + 1, 20));  // ARPACK++ ncv = 0 (auto)
-  EIG_CHECK(nev + 2 <= ncv && ncv <= n && ncv <= 500, EIG_ERR_ARG, "Arnoldi: need nev + 2 <= ncv <= min(n, 500)");
-  if (tol <= 0.0) tol = 2.220446049250313e-16;
-  if (maxit <= 0) maxit = 100 * nev;
-  const int m = ncv;
-  const bool bip = gen && B;  // B-inner product
-  DevBuf Vb((size_t)(m + 1) * n * 8), BVb(bip ? (size_t)(m + 1) * n * 8 : 8), Wb(n * 8), BWb(n * 8), X8b(n * 64),
-      Y8b(n * 64), Tb((size_t)2 * (m + 1) * n * 8), cb((size_t)(m + 8) * 8 * 2);
-  double *V = Vb.d(), *BV = bip ? BVb.d() : Vb.d(), *W = Wb.d(), *BW = BWb.d(), *X8 = X8b.d(), *Y8 = Y8b.d();
-  double *cd = cb.d(), *sc = cd + m + 8;
-  EIG_HIP(hipMemsetAsync(X8, 0, n * 64, s));
-  auto bmul = [&](const double *x, double *y) {  // y = B x
-    if (B) launch_spmv(*B, x, y, nullptr, 0, B->nslices, s);
-    else if (y != x) EIG_HIP(hipMemcpyAsync(y, x, n * 8, hipMemcpyDeviceToDevice, s));
-  };
-  auto dot = [&](const double *x, const double *y) {
-    launch_dot(n, x, y, sc, 0, s, ctx->red);
-    double h = 0.0;
-    EIG_HIP(hipMemcpyAsync(&h, sc, 8, hipMemcpyDeviceToHost, s));
-    EIG_HIP(hipStreamSynchronize(s));
-    return h;
-  };
-  auto solve = [&](const double *bx, double *y) {  // y = (A - sigma B)^-1 bx
-    EIG_HIP(hipMemcpy2DAsync(X8, 64, bx, 8, 8, n, hipMemcpyDeviceToDevice, s));
-    lu_inverse_device(F.lu, 8, X8, Y8, s);
-    EIG_HIP(hipMemcpy2DAsync(y, 8, Y8, 64, 8, n, hipMemcpyDeviceToDevice, s));
-  };
-  auto norm_in = [&](double *x, double *bx) {  // ||x|| in the driver's inner product; bx = B x (bip)
-    if (bip) bmul(x, bx);
-    return std::sqrt(std::max(0.0, dot(x, bip ? bx : x)));
-  };
-  // start vector: mt19937(seed) normal numbers; the generalised mode puts it into range(OP) first
-  // (dgetv0 for mode 3)
-  {
-    std::vector<double> h(n);
-    host_random_normal(n, seed, h.data());
-    EIG_HIP(hipMemcpyAsync(W, h.data(), n * 8, hipMemcpyHostToDevice, s));
-    if (gen)
-    {
-      bmul(W, BW);
-      solve(BW, V);
-    }
-    else
-      EIG_HIP(hipMemcpyAsync(V, W, n * 8, hipMemcpyDeviceToDevice, s));
-    const double nb = norm_in(V, BV);
-    EIG_CHECK(nb > 0.0, EIG_ERR_BREAKDOWN, "Arnoldi: zero start vector");
-    launch_scal(n, 1.0 / nb, V, s);
-    if (bip) launch_scal(n, 1.0 / nb, BV, s);
-  }
-  std::vector<double> G((size_t)m * m, 0.0), cvec, ctot(m + 1);
-  // per step j: the two CGS passes' coefficients and the squared norm of the new vector, on the
-  // device; one read-back per extension (as shift_invert_core)
-  const i64 cstride = 2 * (i64)(m + 1) + 1;
-  DevBuf coefb((size_t)m * cstride * 8);
-  double *coef = coefb.d();
-  std::vector<double> coefh((size_t)m * cstride);
-  std::vector<C> w, Y;
-  std::vector<int> ord(m);
-  double beta = 0.0;
-  int k = 0, nrestart = 0;
-  for (;;)
-  {
-    // extend the Krylov decomposition from k to m vectors (Arnoldi steps)
-    for (int j = k; j < m; ++j)
-    {
-      double *vj = V + (i64)j * n;
-      double *cj = coef + (i64)j * cstride;
-      bmul(vj, BW);
-      solve(BW, W);  // W = OP v_j (the reverse-communication product)
-      for (int pass = 0; pass < 2; ++pass)  // CGS2 against v_0 .. v_j in the inner product
-      {
-        launch_gemv_t(n, j + 1, BV, n, W, cj + pass * (m + 1), 0, s, ctx->red);
-        launch_gemv_n_sub(n, j + 1, V, n, cj + pass * (m + 1), nullptr, W, s);
-      }
-      if (bip) bmul(W, BW);
-      launch_dot(n, W, bip ? BW : W, cj + 2 * (m + 1), 0, s, ctx->red);  // beta_j^2
-      double *vn = V + (i64)(j + 1) * n;
-      EIG_HIP(hipMemcpyAsync(vn, W, n * 8, hipMemcpyDeviceToDevice, s));
-      launch_scal_dev(n, cj + 2 * (m + 1), true, vn, s);
-      if (bip)
-      {
-        double *bvn = BV + (i64)(j + 1) * n;
-        EIG_HIP(hipMemcpyAsync(bvn, BW, n * 8, hipMemcpyDeviceToDevice, s));
-        launch_scal_dev(n, cj + 2 * (m + 1), true, bvn, s);
-      }
-    }
-    EIG_HIP(hipMemcpyAsync(coefh.data() + (size_t)k * cstride, coef + (i64)k * cstride,
-                           (size_t)(m - k) * cstride * 8, hipMemcpyDeviceToHost, s));
-    EIG_HIP(hipStreamSynchronize(s));
-    for (int j = k; j < m; ++j)
-    {
-      if (j > 0)
-        for (int i = 0; i < j; ++i) G[(size_t)j * m + i] = beta * cvec[i];
-      const double *ch = coefh.data() + (size_t)j * cstride;
-      std::fill(ctot.begin(), ctot.end(), 0.0);
-      for (int pass = 0; pass < 2; ++pass)
-        for (int i = 0; i <= j; ++i) ctot[i] += ch[pass * (m + 1) + i];
-      for (int i = 0; i <= j; ++i) G[(size_t)i * m + j] = ctot[i];
-      beta = std::sqrt(std::max(0.0, ch[2 * (m + 1)]));
-      double hn = 0.0;
-      for (int i = 0; i <= j; ++i) hn = std::max(hn, std::fabs(ctot[i]));
-      EIG_CHECK(beta > 1e-14 * hn, EIG_ERR_BREAKDOWN,
-                "Arnoldi: invariant subspace reached (choose ncv < n or another seed)");
-      cvec.assign(j + 1, 0.0);
-      cvec[j] = 1.0;
-    }
-    EIG_CHECK(gen_eig(m, G, w, Y), EIG_ERR_BREAKDOWN, "Arnoldi: QR iteration of the projected matrix failed");
-    // "LM": largest |nu| first (conjugate partners keep their relative order)
-    std::iota(ord.begin(), ord.end(), 0);
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return std::abs(w[a]) > std::abs(w[b]); });
-    auto resid = [&](int q) {
-      C r = 0.0;
-      for (int i = 0; i < m; ++i) r += cvec[i] * Y[(size_t)i * m + q];
-      return beta * std::abs(r);
-    };
-    bool conv = true;
-    for (int i = 0; i < nev; ++i)
-      if (resid(ord[i]) > tol * std::abs(w[ord[i]])) conv = false;
-    if (conv || nrestart >= maxit) break;
-    // Krylov-Schur restart: about nev + (m - nev) / 2 wanted vectors, never splitting a conjugate
-    // pair.  The kept set is built from whole units in "LM" order -- a real Ritz value (one column)
-    // or a conjugate pair (real and imaginary part: two columns; its partner is looked up by value,
-    // wherever the sort put it) -- so span(Z) is G-invariant whatever the ordering of equal moduli.
-    const int target = std::min(m - 2, nev + (m - nev) / 2);
-    std::vector<std::pair<int, bool>> units;  // (eigenvalue index, complex pair)
-    int kk = 0;
-    {
-      std::vector<char> used(m, 0);
-      for (int q = 0; q < m && kk < target; ++q)
-      {
-        const int e = ord[q];
-        if (used[e]) continue;
-        used[e] = 1;
-        const bool cplx = w[e].imag() != 0.0;
-        if (cplx)
-        {
-          int partner = -1;
-          for (int q2 = 0; q2 < m; ++q2)
-            if (!used[ord[q2]] && w[ord[q2]] == std::conj(w[e]))
-            {
-              partner = ord[q2];
-              break;
-            }
-          EIG_CHECK(partner >= 0, EIG_ERR_BREAKDOWN, "Arnoldi: complex Ritz value without its conjugate");
-          used[partner] = 1;
-          if (kk + 2 > m - 1) break;  // a pair that does not fit is dropped whole
-        }
-        units.push_back({e, cplx});
-        kk += cplx ? 2 : 1;
-      }
-    }
-    EIG_CHECK(kk >= 1, EIG_ERR_BREAKDOWN, "Arnoldi: no Ritz vector to keep at restart");
-    std::vector<double> Z((size_t)m * kk, 0.0);  // row-major m x kk
-    {
-      int col = 0;
-      for (auto &u : units)
-      {
-        for (int i = 0; i < m; ++i) Z[(size_t)i * kk + col] = Y[(size_t)i * m + u.first].real();
-        ++col;
-        if (u.second)
-        {
-          for (int i = 0; i < m; ++i) Z[(size_t)i * kk + col] = Y[(size_t)i * m + u.first].imag();
-          ++col;
-        }
-      }
-      for (int c = 0; c < kk; ++c)  // MGS, twice
-        for (int pass = 0; pass < 2; ++pass)
-        {
-          for (int p = 0; p < c; ++p)
-          {
-            double d = 0.0;
-            for (int i = 0; i < m; ++i) d += Z[(size_t)i * kk + p] * Z[(size_t)i * kk + c];
-            for (int i = 0; i < m; ++i) Z[(size_t)i * kk + c] -= d * Z[(size_t)i * kk + p];
-          }
-          double nr = 0.0;
-          for (int i = 0; i < m; ++i) nr += Z[(size_t)i * kk + c] * Z[(size_t)i * kk + c];
-          nr = std::sqrt(nr);
-          EIG_CHECK(nr > 0.0, EIG_ERR_BREAKDOWN, "Arnoldi: dependent Ritz vectors at restart");
-          for (int i = 0; i < m; ++i) Z[(size_t)i * kk + c] /= nr;
-        }
-    }
-    // G <- Z^T G Z, c <- Z^T c; V <- V Z, v_kk <- v_m
-    std::vector<double> GZ((size_t)m * kk, 0.0), Gn((size_t)m * m, 0.0), cn(kk, 0.0);
-    for (int i = 0; i < m; ++i)
-      for (int q = 0; q < kk; ++q)
-      {
-        double a = 0.0;
-        for (int l = 0; l < m; ++l) a += G[(size_t)i * m + l] * Z[(size_t)l * kk + q];
-        GZ[(size_t)i * kk + q] = a;
-      }
-    for (int p = 0; p < kk; ++p)
-    {
-      for (int q = 0; q < kk; ++q)
-      {
-        double a = 0.0;
-        for (int i = 0; i < m; ++i) a += Z[(size_t)i * kk + p] * GZ[(size_t)i * kk + q];
-        Gn[(size_t)p * m + q] = a;
-      }
-      for (int i = 0; i < m; ++i) cn[p] += Z[(size_t)i * kk + p] * cvec[i];
-    }
-    {
-      // the restarted decomposition is a Krylov decomposition only if span(Z) is G-invariant:
-      // ||G Z - Z (Z^T G Z)|| small relative to ||G||
-      double gmax = 0.0, rmax = 0.0;
-      for (double g : G) gmax = std::max(gmax, std::fabs(g));
-      for (int i = 0; i < m; ++i)
-        for (int q = 0; q < kk; ++q)
-        {
-          double a = GZ[(size_t)i * kk + q];
-          for (int p = 0; p < kk; ++p) a -= Z[(size_t)i * kk + p] * Gn[(size_t)p * m + q];
-          rmax = std::max(rmax, std::fabs(a));
-        }
-      EIG_CHECK(rmax <= 1e-6 * std::max(gmax, 1e-300), EIG_ERR_BREAKDOWN,
-                "Arnoldi: restart subspace is not invariant under the projected matrix");
-    }
-    G.swap(Gn);
-    cvec = cn;
-    double *Tmp = Tb.d();
-    std::vector<double> coef(m);
-    for (int q = 0; q < kk; ++q)
-    {
-      for (int i = 0; i < m; ++i) coef[i] = Z[(size_t)i * kk + q];
-      EIG_HIP(hipMemcpyAsync(cd, coef.data(), m * 8, hipMemcpyHostToDevice, s));
-      launch_gemv_n_set(n, m, V, n, cd, nullptr, Tmp + (i64)q * n, s);
-      if (bip) launch_gemv_n_set(n, m, BV, n, cd, nullptr, Tmp + (i64)(kk + q) * n, s);
-      EIG_HIP(hipStreamSynchronize(s));
-    }
-    EIG_HIP(hipMemcpyAsync(V, Tmp, (size_t)kk * n * 8, hipMemcpyDeviceToDevice, s));
-    EIG_HIP(hipMemcpyAsync(V + (i64)kk * n, V + (i64)m * n, n * 8, hipMemcpyDeviceToDevice, s));
-    if (bip)
-    {
-      EIG_HIP(hipMemcpyAsync(BV, Tmp + (i64)kk * n, (size_t)kk * n * 8, hipMemcpyDeviceToDevice, s));
-      EIG_HIP(hipMemcpyAsync(BV + (i64)kk * n, BV + (i64)m * n, n * 8, hipMemcpyDeviceToDevice, s));
-    }
-    k = kk;
-    ++nrestart;
-  }
-  // eigenvalues of the original problem, ascending by real part (:484-498, :556-571)
-  std::vector<C> lam(nev);
-  for (int i = 0; i < nev; ++i)
-  {
-    const C nu = w[ord[i]];
-    lam[i] = gen ? C(sigma) + 1.0 / nu : C(sigma + 1.0 / nu.real(), (C(sigma) + 1.0 / nu).imag());
-  }
-  std::vector<int> idx(nev);
-  std::iota(idx.begin(), idx.end(), 0);
-  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return lam[a].real() < lam[b].real(); });
-  for (int i = 0; i < nev; ++i)
-  {
-    eval_re[i] = lam[idx[i]].real();
-    if (eval_im) eval_im[i] = lam[idx[i]].imag();
-  }
-  if (evec_host)
-  {
-    // x = V y, unit 2-norm as a complex vector; ARPACK's raw storage of a conjugate pair: the real
-    // part for the member with Im(nu) > 0, the imaginary part for its partner
-    std::vector<double> coef(m);
-    for (int q = 0; q < nev; ++q)
-    {
-      const int e = ord[idx[q]];
-      const bool cplx = w[e].imag() != 0.0;
-      int ey = e;
-      if (cplx && w[e].imag() < 0.0)
-        for (int i = 0; i < m; ++i)
-          if (w[i] == std::conj(w[e])) ey = i;
-      double nr2 = 0.0;
-      for (int part = 0; part < (cplx ? 2 : 1); ++part)
-      {
-        for (int i = 0; i < m; ++i)
-          coef[i] = part == 0 ? Y[(size_t)i * m + ey].real() : Y[(size_t)i * m + ey].imag();
-        EIG_HIP(hipMemcpyAsync(cd, coef.data(), m * 8, hipMemcpyHostToDevice, s));
-        launch_gemv_n_set(n, m, V, n, cd, nullptr, part == 0 ? W : BW, s);
-        nr2 += dot(part == 0 ? W : BW, part == 0 ? W : BW);
-      }
-      double *x = (cplx && w[e].imag() < 0.0) ? BW : W;
-      launch_scal(n, 1.0 / std::sqrt(nr2), x, s);
-      EIG_HIP(hipMemcpyAsync(evec_host + (i64)q * n, x, n * 8, hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
-    }
-  }
-  if (restarts) *restarts = nrestart;
-}
-
-}  // namespace
-
-extern "C" int eig_arnoldi_shift_invert(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma, int nev, int ncv,
-                                        double tol, int maxit, unsigned seed, int mode, double *eval_re,
-                                        double *eval_im, double *evec_host, int *restarts)
-{
-  return guard(A ? A->ctx : nullptr, [&] {
-    EIG_CHECK(A && eval_re && nev > 0, EIG_ERR_ARG, "eig_arnoldi_shift_invert: bad argument");
-    EIG_CHECK(mode == EIG_ARNOLDI_STD || mode == EIG_ARNOLDI_GEN, EIG_ERR_ARG, "eig_arnoldi_shift_invert: bad mode");
-    shift_invert_check(A, B);
-    EIG_HIP(hipSetDevice(A->ctx->device));
-    LuRef F;
-    shift_invert_factor(A, B, lu, sigma, F);
-    arnoldi_core(A, B, F, sigma, nev, ncv, tol, maxit, seed, mode == EIG_ARNOLDI_GEN, eval_re, eval_im, evec_host,
-                 restarts);
   });
 }
 
