@@ -1,16 +1,15 @@
-// api.cpp -- the C ABI of libeigmi (include/eigmi.h): contexts, device memory, matrix upload
-// into the SELL-64 image, the halo plan of row-partitioned matrices, BlockVector and
-// MultiVector operations.  Drivers live in drivers.cpp.
+// api.cpp -- the C ABI of libeigmi (include/eigmi.h): contexts, device memory, upload of a matrix's
+// host images (built by mat_image.cpp: SELL-64, symmetric band, slice split), the halo plan of
+// row-partitioned matrices, BlockVector and MultiVector operations.  Drivers live in drivers.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
 #include <mutex>
 #include <random>
-#include <thread>
 
 #include "internal.h"
+#include "mat_image.h"
 
 using namespace eigmi;
 
@@ -983,449 +982,67 @@ extern "C" int eig_memset(eig_ctx_t ctx, void *dst, int value, size_t bytes)
 // ============================================================================================
 namespace {
 
-
-template <class F>
-void parallel_slices(i64 ns, F &&f)
+template <class T>
+T *dev_upload(const T *host, size_t count, hipStream_t s)
 {
-  unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (ns < 4096) nt = 1;
-  if (nt == 1) f(0, ns);
-  else
-  {
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; ++t) th.emplace_back([&, t] { f(ns * t / nt, ns * (t + 1) / nt); });
-    for (auto &t : th) t.join();
-  }
+  T *d = dev_alloc<T>(count);
+  EIG_HIP(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, s));
+  return d;
 }
 
-// Build the SELL-C image (C = 64 R) of `nb` block rows (rowptr/col/vals on the host; columns are
-// shifted by col_shift into window-local block columns; global row = row_begin + r) and upload.
-// 1x1 slices whose rows use at most 8 distinct offsets (col - row) become stencil slices: their
-// value slots are indexed by offset and a per-row mask marks the stored entries (internal.h).
-void build_sell(eig_mat_s &A, i64 nb, const int64_t *rowptr, const int32_t *col, const double *vals, i64 col_shift)
+// The SELL-C image (mat_image.cpp build_sell_image) onto the device; the host image is released on return.
+void upload_sell(eig_mat_s &A, SellImage &&S)
 {
-  const int bb = A.br * A.bc;
   A.R = 1;  // one row per lane (2 / 4 measured slower for the fused Lanczos kernel)
-  const i64 C = 64 * (i64)A.R;
-  const i64 ns = (nb + C - 1) / C;
-  const bool try_stencil = (bb == 1) && !(A.kflags & EIG_MAT_NO_STENCIL);
-  const i64 row0 = A.row_begin;
-  std::vector<i32> swidth(ns, -1), sdelta(8 * (size_t)ns, 0);
-  std::vector<i64> sp(ns + 1, 0), wdt(ns, 0);
-  parallel_slices(ns, [&](i64 s0, i64 s1) {
-    std::vector<i64> offs;
-    for (i64 s = s0; s < s1; ++s)
-    {
-      i64 w = 0;
-      offs.clear();
-      bool ok = try_stencil;
-      for (i64 r = s * C; r < std::min(nb, s * C + C); ++r)
-      {
-        w = std::max<i64>(w, rowptr[r + 1] - rowptr[r]);
-        for (i64 p = rowptr[r]; ok && p < rowptr[r + 1]; ++p)
-        {
-          const i64 d = (i64)col[p] - (row0 + r);
-          if (std::find(offs.begin(), offs.end(), d) == offs.end())
-          {
-            if (offs.size() == 8 || d < INT32_MIN || d > INT32_MAX) ok = false;
-            else offs.push_back(d);
-          }
-        }
-      }
-      if (ok && !offs.empty())
-      {
-        std::sort(offs.begin(), offs.end());
-        swidth[s] = (i32)offs.size();
-        for (size_t k = 0; k < offs.size(); ++k) sdelta[8 * s + k] = (i32)offs[k];
-        w = (i64)offs.size();
-      }
-      wdt[s] = w;
-    }
-  });
-  for (i64 s = 0; s < ns; ++s) sp[s + 1] = sp[s] + C * wdt[s];
-  const i64 total = sp[ns];
-  std::vector<i32> cimg(std::max<i64>(total, 1));
-  std::vector<double> vimg(std::max<i64>(total * bb, 1));
-  std::vector<uint8_t> mimg(try_stencil ? (size_t)(ns * C) : 0, 0);
-  parallel_slices(ns, [&](i64 s0, i64 s1) {
-    for (i64 s = s0; s < s1; ++s)
-    {
-      const i64 base = sp[s], w = (sp[s + 1] - base) / C;
-      for (i64 l = 0; l < C; ++l)
-      {
-        const i64 r = s * C + l;
-        const i64 len = (r < nb) ? rowptr[r + 1] - rowptr[r] : 0;
-        for (i64 k = 0; k < w; ++k)
-        {
-          cimg[base + k * C + l] = -1;
-          for (int t = 0; t < bb; ++t) vimg[(base + k * C) * bb + t * C + l] = 0.0;
-        }
-        for (i64 e = 0; e < len; ++e)
-        {
-          const i64 p = rowptr[r] + e;
-          i64 k = e;
-          if (swidth[s] > 0)
-          {
-            const i64 d = (i64)col[p] - (row0 + r);
-            k = std::find(&sdelta[8 * s], &sdelta[8 * s] + swidth[s], (i32)d) - &sdelta[8 * s];
-            mimg[s * C + l] |= (uint8_t)(1u << k);
-          }
-          cimg[base + k * C + l] = (i32)(col[p] - col_shift);
-          for (int t = 0; t < bb; ++t) vimg[(base + k * C) * bb + t * C + l] = vals[p * bb + t];
-        }
-      }
-    }
-  });
-  {
-    std::vector<i64> bw(16, 0);
-    const i64 nt = std::min<i64>(16, std::max<i64>(1, nb / 65536));
-    std::vector<std::thread> th;
-    for (i64 t = 0; t < nt; ++t)
-      th.emplace_back([&, t] {
-        i64 m = 0;
-        for (i64 r = nb * t / nt; r < nb * (t + 1) / nt; ++r)
-          for (i64 p = rowptr[r]; p < rowptr[r + 1]; ++p) m = std::max<i64>(m, std::llabs((i64)col[p] - (row0 + r)));
-        bw[t] = m;
-      });
-    for (auto &x : th) x.join();
-    A.bandwidth = *std::max_element(bw.begin(), bw.end());
-  }
+  const i64 C = 64 * (i64)A.R, ns = S.nslices, total = S.nnzb_padded, bb = A.br * A.bc;
+  hipStream_t s = A.ctx->stream;
+  A.bandwidth = S.bandwidth;
   A.nslices = ns;
   A.nnzb_padded = total;
-  A.slice_ptr = dev_alloc<i64>(ns + 1);
-  A.col = dev_alloc<i32>(total);
-  A.val = dev_alloc<double>(total * bb);
-  hipStream_t s = A.ctx->stream;
-  EIG_HIP(hipMemcpyAsync(A.slice_ptr, sp.data(), (ns + 1) * sizeof(i64), hipMemcpyHostToDevice, s));
-  EIG_HIP(hipMemcpyAsync(A.col, cimg.data(), total * sizeof(i32), hipMemcpyHostToDevice, s));
-  EIG_HIP(hipMemcpyAsync(A.val, vimg.data(), total * bb * sizeof(double), hipMemcpyHostToDevice, s));
-  A.n_stencil_slices = 0;
-  A.sell_explicit = 0;
-  for (i64 q = 0; q < ns; ++q)
-  {
-    A.n_stencil_slices += swidth[q] > 0;
-    if (swidth[q] <= 0) A.sell_explicit += sp[q + 1] - sp[q];
-  }
+  A.slice_ptr = dev_upload(S.slice_ptr.data(), ns + 1, s);
+  A.col = dev_upload(S.col.data(), total, s);
+  A.val = dev_upload(S.val.data(), total * bb, s);
+  A.n_stencil_slices = S.n_stencil_slices;
+  A.sell_explicit = S.sell_explicit;
   if (A.n_stencil_slices > 0)
   {
-    A.st_width = dev_alloc<i32>(ns);
-    A.st_delta = dev_alloc<i32>(8 * ns);
-    A.st_mask = dev_alloc<uint8_t>(ns * C);
-    EIG_HIP(hipMemcpyAsync(A.st_width, swidth.data(), ns * sizeof(i32), hipMemcpyHostToDevice, s));
-    EIG_HIP(hipMemcpyAsync(A.st_delta, sdelta.data(), 8 * ns * sizeof(i32), hipMemcpyHostToDevice, s));
-    EIG_HIP(hipMemcpyAsync(A.st_mask, mimg.data(), ns * C, hipMemcpyHostToDevice, s));
+    A.st_width = dev_upload(S.st_width.data(), ns, s);
+    A.st_delta = dev_upload(S.st_delta.data(), 8 * ns, s);
+    A.st_mask = dev_upload(S.st_mask.data(), ns * C, s);
   }
   EIG_HIP(hipStreamSynchronize(s));
   A.device_bytes = (ns + 1) * 8 + total * 4 + total * bb * 8 + (A.n_stencil_slices ? ns * (36 + C) : 0);
 }
 
-
-// Symmetric band image (internal.h, eig_mat_s::sym_*) next to the SELL image, for square 1x1
-// matrices with at most kSymMaxOff distinct offsets whose stored mirror pairs are bitwise equal
-// and whose band arrays are smaller than the SELL values.  Pass 1 (rows in parallel) stores each
-// row's entries at d >= 0 in slot [j(d)][w]; pass 2 stores the entries at d < 0 in slot
-// [j(-d)][w + d], which only the mirror (row w + d, offset -d) of pass 1 can also own -- a set
-// slot with different bits rejects the image.  Ghost rows below the owned range (distributed)
-// get their slots from the owned rows' lower entries alone.  Silently skipped when not applicable.
-void build_sym(eig_mat_s &A, i64 nb, const int64_t *rowptr, const int32_t *col, const double *vals)
+// The symmetric band image (mat_image.cpp build_sym_image) onto the device, where it was built.
+void upload_sym(eig_mat_s &A, SymImage &&S)
 {
-  if (A.br != 1 || A.bc != 1 || (A.kflags & EIG_MAT_NO_BAND) || nb == 0) return;
-  if (A.nb_cols != A.nb_rows_global) return;
-  const i64 row0 = A.row_begin;
-  // distinct offsets (per thread, then merged)
-  std::vector<i64> offs;
-  {
-    std::mutex mu;
-    bool ok = true;
-    parallel_slices(nb, [&](i64 r0, i64 r1) {
-      std::vector<i64> mine;
-      for (i64 r = r0; r < r1 && mine.size() <= (size_t)kSymMaxOff; ++r)
-        for (i64 p = rowptr[r]; p < rowptr[r + 1]; ++p)
-        {
-          const i64 d = (i64)col[p] - (row0 + r);
-          if (std::find(mine.begin(), mine.end(), d) == mine.end()) mine.push_back(d);
-        }
-      std::lock_guard<std::mutex> lk(mu);
-      if (mine.size() > (size_t)kSymMaxOff) ok = false;
-      for (i64 d : mine)
-        if (std::find(offs.begin(), offs.end(), d) == offs.end()) offs.push_back(d);
-    });
-    if (!ok || offs.size() > (size_t)kSymMaxOff || offs.empty()) return;
-  }
-  std::sort(offs.begin(), offs.end());
-  std::vector<i64> ups;
-  for (i64 d : offs)
-  {
-    if (d < INT32_MIN || d > INT32_MAX) return;
-    const i64 a = std::llabs(d);
-    if (std::find(ups.begin(), ups.end(), a) == ups.end()) ups.push_back(a);
-  }
-  std::sort(ups.begin(), ups.end());
-  const int nd = (int)offs.size(), nup = (int)ups.size();
-  const i64 ns = A.nslices, own = A.own_offset;
-  const i64 ld = ((std::max<i64>(A.window, own + ns * 64) + 63) / 64) * 64;
-  // only worth it when the band arrays are smaller than the SELL values the kernels would stream
-  if ((double)nup * (double)ld > 0.9 * (double)A.nnzb_padded) return;
-  auto jof = [&](i64 a) { return (int)(std::lower_bound(ups.begin(), ups.end(), a) - ups.begin()); };
-  std::vector<int> kj(nd);
-  for (int k = 0; k < nd; ++k) kj[k] = jof(std::llabs(offs[k]));
-  std::vector<double> U((size_t)nup * ld, 0.0);
-  std::vector<uint8_t> set((size_t)nup * ld, 0);
-  const int mb = nd <= 8 ? 1 : 4;
-  std::vector<uint8_t> m8(mb == 1 ? (size_t)ns * 64 : 0, 0);
-  std::vector<uint32_t> m32(mb == 4 ? (size_t)ns * 64 : 0, 0);
-  std::atomic<bool> good{true};
-  auto kof = [&](i64 d) { return (int)(std::lower_bound(offs.begin(), offs.end(), d) - offs.begin()); };
-  parallel_slices(nb, [&](i64 r0, i64 r1) {
-    for (i64 r = r0; r < r1; ++r)
-    {
-      uint32_t m = 0;
-      for (i64 p = rowptr[r]; p < rowptr[r + 1]; ++p)
-      {
-        const i64 d = (i64)col[p] - (row0 + r);
-        const int k = kof(d);
-        m |= 1u << k;
-        if (d >= 0)
-        {
-          const size_t q = (size_t)kj[k] * ld + (size_t)(own + r);
-          U[q] = vals[p];
-          set[q] = 1;
-        }
-      }
-      if (mb == 1) m8[r] = (uint8_t)m;
-      else m32[r] = m;
-    }
-  });
-  parallel_slices(nb, [&](i64 r0, i64 r1) {
-    for (i64 r = r0; r < r1 && good.load(std::memory_order_relaxed); ++r)
-      for (i64 p = rowptr[r]; p < rowptr[r + 1]; ++p)
-      {
-        const i64 d = (i64)col[p] - (row0 + r);
-        if (d >= 0) break;  // ascending columns: the rest are upper entries
-        const i64 x = own + r + d;
-        if (x < 0 || x >= ld)
-        {
-          good = false;
-          break;
-        }
-        const size_t q = (size_t)kj[kof(d)] * ld + (size_t)x;
-        if (set[q])
-        {
-          if (std::memcmp(&U[q], &vals[p], sizeof(double)) != 0)
-          {
-            good = false;
-            break;
-          }
-        }
-        else
-          U[q] = vals[p];
-      }
-  });
-  if (!good) return;
-  // uniform band: one value per array over every stored entry, lower entries included (a lower entry
-  // whose mirror is not stored on this rank -- a ghost row's coupling, or a one-sided pattern -- was
-  // never compared in the mirror pass, and the uniform march kernels take the array's constant for it)
-  {
-    std::mutex mu;
-    std::vector<double> uc(nup, 0.0);
-    std::vector<char> seen(nup, 0);
-    bool uni = true;
-    parallel_slices(nb, [&](i64 r0, i64 r1) {
-      std::vector<double> v(nup, 0.0);
-      std::vector<char> sn(nup, 0);
-      bool ok = true;
-      for (i64 r = r0; r < r1 && ok; ++r)
-        for (i64 p = rowptr[r]; p < rowptr[r + 1]; ++p)
-        {
-          const i64 d = (i64)col[p] - (row0 + r);
-          const int j = kj[kof(d)];
-          if (!sn[j])
-          {
-            sn[j] = 1;
-            v[j] = vals[p];
-          }
-          else if (std::memcmp(&v[j], &vals[p], sizeof(double)) != 0)
-          {
-            ok = false;
-            break;
-          }
-        }
-      std::lock_guard<std::mutex> lk(mu);
-      uni = uni && ok;
-      for (int j = 0; j < nup && uni; ++j)
-        if (sn[j])
-        {
-          if (!seen[j])
-          {
-            seen[j] = 1;
-            uc[j] = v[j];
-          }
-          else if (std::memcmp(&uc[j], &v[j], sizeof(double)) != 0)
-            uni = false;
-        }
-    });
-    A.sym_uniform = uni;
-    for (int j = 0; j < nup; ++j) A.sym_uc[j] = uni ? uc[j] : 0.0;
-  }
-  // geometric masks: a grid whose rows store exactly their in-grid neighbours -- the whole grid on
-  // one rank, or a rank's slab of whole planes (row0 and nb multiples of the plane size D; z is
-  // the global plane, so the slab's first / last planes keep their ghost-plane bits).  A property of
-  // the pattern alone: the uniform marches take the values from their arguments, the value march
-  // (march variant 10) streams them from the band arrays.
-  A.sym_geo = false;
-  if (mb == 1 && offs.front() == -offs.back() && (nd == 7 || nd == 5))
-  {
-    const i64 D = offs.back();
-    const i64 nx = nd == 7 ? offs[5] : D;
-    bool shape = D > 1 && nx > 1 && D % nx == 0 && nb % D == 0 && row0 % D == 0 && A.nb_rows_global % D == 0 &&
-                 (nd == 5 || (offs[4] == 1 && offs[2] == -1 && offs[1] == -nx && nx < D));
-    if (nd == 5) shape = shape && offs[1] == -1 && offs[3] == 1;
-    if (shape)
-    {
-      const i64 ny = D / nx, nz = A.nb_rows_global / D;
-      std::atomic<bool> same{true};
-      parallel_slices(nb, [&](i64 r0, i64 r1) {
-        for (i64 r = r0; r < r1 && same.load(std::memory_order_relaxed); ++r)
-        {
-          const i64 g = row0 + r;
-          const i64 x = g % nx, y = (g / nx) % ny, z = g / D;
-          unsigned e = 0;
-          int k = 0;
-          e |= (z > 0 ? 1u : 0u) << k++;
-          if (nd == 7) e |= (y > 0 ? 1u : 0u) << k++;
-          e |= (x > 0 ? 1u : 0u) << k++;
-          e |= 1u << k++;
-          e |= (x < nx - 1 ? 1u : 0u) << k++;
-          if (nd == 7) e |= (y < ny - 1 ? 1u : 0u) << k++;
-          e |= (z < nz - 1 ? 1u : 0u) << k++;
-          if (e != m8[r]) same = false;
-        }
-      });
-      if (same && nx <= INT32_MAX && ny <= INT32_MAX && nz <= INT32_MAX)
-      {
-        A.sym_geo = true;
-        A.sym_gx = (int)nx;
-        A.sym_gy = (int)ny;
-        A.sym_gz = (int)nz;
-        A.sym_gz0 = (int)(row0 / D);
-      }
-    }
-  }
-  // box-geometric masks (general 27-point box subsets, e.g. the P1 Kuhn 15-point stencil): decompose the
-  // offsets as a D + b nx + c -- nx the smallest offset > 1 (or that + 1 when (0, 1, -1) is stored), D
-  // the smallest offset past nx + 1 (or that + 1, + nx - 1, + nx, + nx + 1) -- then check row by row
-  A.sym_box27 = 0;
-  if (!A.sym_geo && nd >= 3 && nd <= 27 && offs.front() == -offs.back())
-  {
-    i64 s1 = 0;
-    for (i64 d : offs)
-      if (d > 1 && (s1 == 0 || d < s1)) s1 = d;
-    std::vector<int> bx(nd), by(nd), bz(nd);
-    auto decompose = [&](i64 nxc, i64 Dc) {
-      for (int k = 0; k < nd; ++k)
-      {
-        bool found = false;
-        for (int a = -1; a <= 1 && !found; ++a)
-          for (int b2 = -1; b2 <= 1 && !found; ++b2)
-            for (int c = -1; c <= 1 && !found; ++c)
-              if (a * Dc + b2 * nxc + c == offs[k]) bz[k] = a, by[k] = b2, bx[k] = c, found = true;
-        if (!found) return false;
-      }
-      return true;
-    };
-    i64 gnx = 0, gD = 0;
-    for (i64 nxc : {s1, s1 + 1})
-    {
-      if (nxc < 3 || gD) continue;
-      i64 t = 0;
-      for (i64 d : offs)
-        if (d > nxc + 1 && (t == 0 || d < t)) t = d;
-      if (t == 0) continue;
-      for (i64 Dc : {t, t + 1, t + nxc - 1, t + nxc, t + nxc + 1})
-        if (!gD && Dc % nxc == 0 && Dc / nxc >= 3 && A.nb_rows_global % Dc == 0 && nb % Dc == 0 && row0 % Dc == 0 &&
-            decompose(nxc, Dc))
-          gnx = nxc, gD = Dc;
-    }
-    if (gD && A.nb_rows_global / gD >= 3 && gnx <= INT32_MAX && gD / gnx <= INT32_MAX &&
-        A.nb_rows_global / gD <= INT32_MAX)
-    {
-      decompose(gnx, gD);
-      const i64 gny = gD / gnx, gnz = A.nb_rows_global / gD;
-      std::atomic<bool> same{true};
-      parallel_slices(nb, [&](i64 r0, i64 r1) {
-        for (i64 r = r0; r < r1 && same.load(std::memory_order_relaxed); ++r)
-        {
-          const i64 g = row0 + r;
-          const i64 x = g % gnx, y = (g / gnx) % gny, z = g / gD;
-          uint32_t e = 0;
-          for (int k = 0; k < nd; ++k)
-          {
-            const i64 xx = x + bx[k], yy = y + by[k], zz = z + bz[k];
-            if (xx >= 0 && xx < gnx && yy >= 0 && yy < gny && zz >= 0 && zz < gnz) e |= 1u << k;
-          }
-          if (e != (mb == 1 ? (uint32_t)m8[r] : m32[r])) same = false;
-        }
-      });
-      if (same)
-      {
-        for (int k = 0; k < nd; ++k) A.sym_box27 |= 1u << ((bz[k] + 1) * 9 + (by[k] + 1) * 3 + (bx[k] + 1));
-        A.sym_gx = (int)gnx;
-        A.sym_gy = (int)gny;
-        A.sym_gz = (int)gnz;
-        A.sym_gz0 = (int)(row0 / gD);
-      }
-    }
-  }
+  if (!S.built) return;
+  const i64 ns = A.nslices;
+  const int mb = S.mask_bytes;
   hipStream_t s = A.ctx->stream;
-  A.sym_val = dev_alloc<double>((size_t)nup * ld);
-  A.sym_mask = mb == 1 ? (void *)dev_alloc<uint8_t>(ns * 64) : (void *)dev_alloc<uint32_t>(ns * 64);
-  EIG_HIP(hipMemcpyAsync(A.sym_val, U.data(), (size_t)nup * ld * sizeof(double), hipMemcpyHostToDevice, s));
-  EIG_HIP(hipMemcpyAsync(A.sym_mask, mb == 1 ? (const void *)m8.data() : (const void *)m32.data(), ns * 64 * mb,
-                         hipMemcpyHostToDevice, s));
+  A.sym_uniform = S.uniform;
+  A.sym_geo = S.geo;
+  A.sym_box27 = S.box27;
+  A.sym_gx = S.gx;
+  A.sym_gy = S.gy;
+  A.sym_gz = S.gz;
+  A.sym_gz0 = S.gz0;
+  A.sym_val = dev_upload(S.val.data(), (size_t)S.nup * S.ld, s);
+  A.sym_mask = mb == 1 ? (void *)dev_upload(S.mask8.data(), ns * 64, s)
+                       : (void *)dev_upload(S.mask32.data(), ns * 64, s);
   EIG_HIP(hipStreamSynchronize(s));
   A.sym_mask_bytes = mb;
-  A.sym_nd = nd;
-  A.sym_nup = nup;
-  A.sym_ld = ld;
-  for (int k = 0; k < nd; ++k)
+  A.sym_nd = S.nd;
+  A.sym_nup = S.nup;
+  A.sym_ld = S.ld;
+  for (int k = 0; k < S.nd; ++k)
   {
-    A.sym_off[k] = (i32)offs[k];
-    A.sym_dj[k] = kj[k];
+    A.sym_off[k] = S.off[k];
+    A.sym_dj[k] = S.dj[k];
   }
-  A.device_bytes += (i64)nup * ld * 8 + ns * 64 * mb;
-}
-
-void validate_csr(i64 nb, i64 ncols, const int64_t *rowptr, const int32_t *col)
-{
-  EIG_CHECK(rowptr[0] == 0, EIG_ERR_ARG, "rowptr[0] must be 0");
-  for (i64 r = 0; r < nb; ++r)
-  {
-    EIG_CHECK(rowptr[r + 1] >= rowptr[r], EIG_ERR_ARG, "rowptr must be non-decreasing");
-    for (i64 p = rowptr[r]; p < rowptr[r + 1]; ++p)
-    {
-      EIG_CHECK(col[p] >= 0 && col[p] < ncols, EIG_ERR_SHAPE, "column index out of range");
-      if (p > rowptr[r]) EIG_CHECK(col[p] > col[p - 1], EIG_ERR_ARG, "columns must be strictly ascending per row");
-    }
-  }
-}
-
-// Diagonal share of the owned rows (global row = row_begin + r): sum of the stored diagonal
-// entries of the diagonal blocks and the number of scalar rows that store one.
-void diag_share(eig_mat_s &A, i64 nb, i64 row_begin, const int64_t *rowptr, const int32_t *col, const double *vals)
-{
-  const int br = A.br, bc = A.bc;
-  double s = 0.0;
-  i64 cnt = 0;
-  for (i64 r = 0; r < nb; ++r)
-    for (i64 p = rowptr[r]; p < rowptr[r + 1]; ++p)
-      if (col[p] == row_begin + r)
-        for (int i = 0; i < std::min(br, bc); ++i)
-        {
-          s += vals[p * br * bc + (i64)i * bc + i];
-          ++cnt;
-        }
-  A.diag_sum = s;
-  A.diag_count = cnt;
+  for (int j = 0; j < S.nup; ++j) A.sym_uc[j] = S.uc[j];
+  A.device_bytes += (i64)S.nup * S.ld * 8 + ns * 64 * mb;
 }
 
 void destroy_mat(eig_mat_s *A)
@@ -1446,6 +1063,84 @@ void destroy_mat(eig_mat_s *A)
   if (A->box_ctab) (void)hipFree(A->box_ctab);
   if (A->box_cmask) (void)hipFree(A->box_cmask);
   delete A;
+}
+
+// A new matrix of shape `sh` with the images of its `nb` owned rows (columns shifted by col_shift block columns
+// into the window); `finish` completes it (the halo plan of a distributed matrix).  The SELL image is built,
+// uploaded and released before the band image is built: the two never share the host.
+template <class F>
+eig_mat_s *create_mat(eig_ctx_t ctx, const MatShape &sh, i64 nb, i64 col_shift, const int64_t *rowptr,
+                      const int32_t *col, const double *vals, F &&finish)
+{
+  auto *A = new eig_mat_s();
+  A->ctx = ctx;
+  A->kflags = sh.kflags;
+  A->br = sh.br;
+  A->bc = sh.bc;
+  A->nb_rows = nb;
+  A->nb_rows_global = sh.nb_rows_global;
+  A->nb_cols = sh.nb_cols;
+  A->row_begin = sh.row_begin;
+  A->win_begin = col_shift * sh.bc;
+  A->window = sh.window;
+  A->own_offset = sh.own_offset;
+  A->nnzb = rowptr[nb];
+  try
+  {
+    upload_sell(*A, build_sell_image(sh, nb, rowptr, col, vals, col_shift));
+    upload_sym(*A, build_sym_image(sh, A->nslices, A->nnzb_padded, nb, rowptr, col, vals));
+    const DiagShare d = diag_share(sh.br, sh.bc, nb, sh.row_begin, rowptr, col, vals);
+    A->diag_sum = d.sum;
+    A->diag_count = d.count;
+    finish(*A);
+  }
+  catch (...)
+  {
+    destroy_mat(A);
+    throw;
+  }
+  return A;
+}
+
+// Allgather of every rank's 4 values `mine` (row_begin, nb_local, cmin, cmax) over the context's transport.
+std::vector<i64> allgather_rows(eig_ctx_t ctx, const std::vector<i64> &mine)
+{
+  const int P = ctx->nranks, me = ctx->rank;
+  std::vector<i64> all(4 * (size_t)P, 0);
+  if (ctx->loop && P > 1)
+  {
+    LoopHub &h = *ctx->loop;
+    {
+      std::lock_guard<std::mutex> lk(h.m);
+      for (int t = 0; t < 4; ++t) h.gather[4 * me + t] = mine[t];
+    }
+    h.barrier();
+    all = h.gather;
+    h.barrier();
+  }
+  else if (!ctx->comm && P > 1 && ctx->mbox && ctx->mbox->ready)
+  {
+    // mailbox-only ranks (eig_comm_ipc_open): an allgather as an allreduce of zero-padded rows
+    // (integers below 2^53: the double sums are exact)
+    std::vector<double> g(4 * (size_t)P, 0.0);
+    for (int t = 0; t < 4; ++t) g[4 * me + t] = (double)mine[t];
+    mailbox_sum_sync(ctx, g, "eig_mat_create_bcsr_dist");
+    for (size_t t = 0; t < g.size(); ++t) all[t] = (i64)g[t];
+  }
+  else if (ctx->comm && P > 1)
+  {
+    i64 *d = dev_alloc<i64>(4 * (size_t)P);
+    EIG_HIP(hipMemcpy(d + 4 * me, mine.data(), 4 * sizeof(i64), hipMemcpyHostToDevice));
+    EIG_NCCL(ncclAllGather(d + 4 * me, d, 4 * sizeof(i64), ncclChar, ctx->comm, ctx->stream));
+    EIG_HIP(hipStreamSynchronize(ctx->stream));
+    EIG_HIP(hipMemcpy(all.data(), d, 4 * P * sizeof(i64), hipMemcpyDeviceToHost));
+    (void)hipFree(d);
+  }
+  else
+  {
+    all = mine;
+  }
+  return all;
 }
 
 }  // namespace
@@ -1469,30 +1164,14 @@ extern "C" int eig_mat_create_bcsr_ex(eig_ctx_t ctx, int64_t nb_rows, int64_t nb
     EIG_CHECK(nb_cols * bc < (int64_t)INT32_MAX, EIG_ERR_SHAPE, "matrix too large for int32 column indices");
     DeviceGuard dg(ctx->device);
     validate_csr(nb_rows, nb_cols, rowptr, col);
-    auto *A = new eig_mat_s();
-    A->ctx = ctx;
-    A->kflags = flags;
-    A->br = br;
-    A->bc = bc;
-    A->nb_rows = A->nb_rows_global = nb_rows;
-    A->nb_cols = nb_cols;
-    A->row_begin = 0;
-    A->win_begin = 0;
-    A->window = nb_cols * bc;
-    A->own_offset = 0;
-    A->nnzb = rowptr[nb_rows];
-    try
-    {
-      build_sell(*A, nb_rows, rowptr, col, vals, 0);
-      build_sym(*A, nb_rows, rowptr, col, vals);
-      diag_share(*A, nb_rows, 0, rowptr, col, vals);
-    }
-    catch (...)
-    {
-      destroy_mat(A);
-      throw;
-    }
-    *out = A;
+    MatShape sh;
+    sh.br = br;
+    sh.bc = bc;
+    sh.kflags = flags;
+    sh.nb_rows_global = nb_rows;
+    sh.nb_cols = nb_cols;
+    sh.window = nb_cols * bc;
+    *out = create_mat(ctx, sh, nb_rows, 0, rowptr, col, vals, [](eig_mat_s &) {});
   });
 }
 
@@ -1523,70 +1202,17 @@ extern "C" int eig_mat_create_bcsr_dist_ex(eig_ctx_t ctx, int64_t nb_rows_global
       EIG_CHECK(rc == EIG_OK, rc, "eig_plan_window failed");
     }
     const i64 wb_blk = plan[0], cmin = plan[3], cmax = plan[4];
-    auto *A = new eig_mat_s();
-    A->ctx = ctx;
-    A->kflags = flags;
-    A->br = br;
-    A->bc = bc;
-    A->nb_rows = nb_local;
-    A->nb_rows_global = nb_rows_global;
-    A->nb_cols = nb_rows_global;
-    A->row_begin = row_begin;
-    A->win_begin = wb_blk * bc;
-    A->window = plan[1];
-    A->own_offset = plan[2];
-    A->nnzb = rowptr[nb_local];
-    try
-    {
-      build_sell(*A, nb_local, rowptr, col, vals, wb_blk);
-      build_sym(*A, nb_local, rowptr, col, vals);
-      diag_share(*A, nb_local, row_begin, rowptr, col, vals);
+    MatShape sh;
+    sh.br = br;
+    sh.bc = bc;
+    sh.kflags = flags;
+    sh.nb_rows_global = sh.nb_cols = nb_rows_global;
+    sh.row_begin = row_begin;
+    sh.window = plan[1];
+    sh.own_offset = plan[2];
+    *out = create_mat(ctx, sh, nb_local, wb_blk, rowptr, col, vals, [&](eig_mat_s &A) {
       // --- halo plan: allgather (row_begin, nb_local, cmin, cmax) of every rank ---
-      std::vector<i64> mine = {row_begin, nb_local, cmin, cmax};
-      std::vector<i64> all(4 * (size_t)P, 0);
-      if (ctx->loop && P > 1)
-      {
-        LoopHub &h = *ctx->loop;
-        {
-          std::lock_guard<std::mutex> lk(h.m);
-          for (int t = 0; t < 4; ++t) h.gather[4 * me + t] = mine[t];
-        }
-        h.barrier();
-        all = h.gather;
-        h.barrier();
-      }
-      else if (!ctx->comm && P > 1 && ctx->mbox && ctx->mbox->ready)
-      {
-        // mailbox-only ranks (eig_comm_ipc_open): an allgather as an allreduce of zero-padded rows
-        // (integers below 2^53: the double sums are exact)
-        std::vector<double> g(4 * (size_t)P, 0.0);
-        for (int t = 0; t < 4; ++t) g[4 * me + t] = (double)mine[t];
-        double *d = dev_alloc<double>(g.size());
-        EIG_HIP(hipMemcpy(d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
-        for (i64 off = 0; off < (i64)g.size(); off += kMailboxVals)
-          launch_mailbox_allreduce(d + off, (int)std::min<i64>(kMailboxVals, (i64)g.size() - off), ctx->mbox->dev,
-                                   kMailboxTimeout, ctx->stream);
-        EIG_HIP(hipStreamSynchronize(ctx->stream));
-        EIG_HIP(hipMemcpy(g.data(), d, g.size() * sizeof(double), hipMemcpyDeviceToHost));
-        (void)hipFree(d);
-        int err = 0;
-        EIG_HIP(hipMemcpy(&err, ctx->mbox->dev.err, sizeof(int), hipMemcpyDeviceToHost));
-        EIG_CHECK(err == 0, EIG_ERR_RCCL, "eig_mat_create_bcsr_dist: mailbox allgather timed out");
-        for (size_t t = 0; t < g.size(); ++t) all[t] = (i64)g[t];
-      }
-      else if (ctx->comm && P > 1)
-      {
-        i64 *d = dev_alloc<i64>(4 * (size_t)P);
-        EIG_HIP(hipMemcpy(d + 4 * me, mine.data(), 4 * sizeof(i64), hipMemcpyHostToDevice));
-        EIG_NCCL(ncclAllGather(d + 4 * me, d, 4 * sizeof(i64), ncclChar, ctx->comm, ctx->stream));
-        EIG_HIP(hipStreamSynchronize(ctx->stream));
-        EIG_HIP(hipMemcpy(all.data(), d, 4 * P * sizeof(i64), hipMemcpyDeviceToHost));
-        (void)hipFree(d);
-      }
-      else
-      {
-        all = mine;
-      }
+      const std::vector<i64> all = allgather_rows(ctx, {row_begin, nb_local, cmin, cmax});
       const int nr = ctx->distributed() ? P : 1;
       std::vector<int64_t> rv(3 * (size_t)nr), sd(3 * (size_t)nr);
       int nrecv = 0, nsend = 0;
@@ -1628,77 +1254,30 @@ extern "C" int eig_mat_create_bcsr_dist_ex(eig_ctx_t ctx, int64_t nb_rows_global
           }
         }
       }
-      for (int k = 0; k < nrecv; ++k) A->recvs.push_back({(int)rv[3 * k], rv[3 * k + 1], rv[3 * k + 2]});
-      for (int k = 0; k < nsend; ++k) A->sends.push_back({(int)sd[3 * k], sd[3 * k + 1], sd[3 * k + 2]});
-      for (auto &r : A->recvs) A->halo_recv += r.count;
-      for (auto &r : A->sends) A->halo_send += r.count;
-      // interior / boundary slices: a slice is interior when every column is owned
-      std::vector<i32> inter, bound;
-      const i64 own_lo = row_begin, own_hi = row_begin + nb_local;
-      for (i64 s = 0; s < A->nslices; ++s)
-      {
-        bool in = true;
-        const i64 C = 64 * (i64)A->R;
-        for (i64 r = s * C; r < std::min(nb_local, s * C + C) && in; ++r)
-          for (i64 p = rowptr[r]; p < rowptr[r + 1]; ++p)
-            if (col[p] < own_lo || col[p] >= own_hi)
-            {
-              in = false;
-              break;
-            }
-        (in ? inter : bound).push_back((i32)s);
-      }
-      A->n_interior = (i64)inter.size();
-      A->n_boundary = (i64)bound.size();
-      std::vector<i32> lst(inter);
-      lst.insert(lst.end(), bound.begin(), bound.end());
-      A->slice_list = dev_alloc<i32>(std::max<size_t>(lst.size(), 1));
-      if (!lst.empty()) EIG_HIP(hipMemcpy(A->slice_list, lst.data(), lst.size() * sizeof(i32), hipMemcpyHostToDevice));
-      // plane-march split: the longest run of planes whose slices are all interior (>= 2 planes)
+      for (int k = 0; k < nrecv; ++k) A.recvs.push_back({(int)rv[3 * k], rv[3 * k + 1], rv[3 * k + 2]});
+      for (int k = 0; k < nsend; ++k) A.sends.push_back({(int)sd[3 * k], sd[3 * k + 1], sd[3 * k + 2]});
+      for (auto &r : A.recvs) A.halo_recv += r.count;
+      for (auto &r : A.sends) A.halo_send += r.count;
+      // interior / boundary slices and the plane-march split (planes of D rows) of the interior planes
       i64 D;
-      if (march_geometry(*A, D))
+      if (!march_geometry(A, D)) D = 0;
+      const SliceSplit sp = split_slices(A.nslices, nb_local, row_begin, rowptr, col, D);
+      A.n_interior = (i64)sp.interior.size();
+      A.n_boundary = (i64)sp.boundary.size();
+      std::vector<i32> lst(sp.interior);
+      lst.insert(lst.end(), sp.boundary.begin(), sp.boundary.end());
+      A.slice_list = dev_alloc<i32>(std::max<size_t>(lst.size(), 1));
+      if (!lst.empty()) EIG_HIP(hipMemcpy(A.slice_list, lst.data(), lst.size() * sizeof(i32), hipMemcpyHostToDevice));
+      if (sp.mz1 - sp.mz0 >= 2)
       {
-        const i64 spp = D / 64, np = (nb_local + D - 1) / D;
-        std::vector<char> is_in(A->nslices, 0);
-        for (i32 q : inter) is_in[q] = 1;
-        i64 best0 = 0, best1 = 0;
-        for (i64 z = 0; z < np;)
-        {
-          auto plane_in = [&](i64 zz) {
-            for (i64 q = zz * spp; q < std::min(A->nslices, (zz + 1) * spp); ++q)
-              if (!is_in[q]) return false;
-            return true;
-          };
-          if (!plane_in(z))
-          {
-            ++z;
-            continue;
-          }
-          i64 e = z;
-          while (e < np && plane_in(e)) ++e;
-          if (e - z > best1 - best0) best0 = z, best1 = e;
-          z = e;
-        }
-        if (best1 - best0 >= 2)
-        {
-          std::vector<i32> bnd;
-          for (i64 q = 0; q < A->nslices; ++q)
-            if (q < best0 * spp || q >= best1 * spp) bnd.push_back((i32)q);
-          A->mz0 = best0;
-          A->mz1 = best1;
-          A->n_march_bnd = (i64)bnd.size();
-          A->march_bnd = dev_alloc<i32>(std::max<size_t>(bnd.size(), 1));
-          if (!bnd.empty())
-            EIG_HIP(hipMemcpy(A->march_bnd, bnd.data(), bnd.size() * sizeof(i32), hipMemcpyHostToDevice));
-        }
+        const std::vector<i32> &bnd = sp.march_bnd;
+        A.mz0 = sp.mz0;
+        A.mz1 = sp.mz1;
+        A.n_march_bnd = (i64)bnd.size();
+        A.march_bnd = dev_alloc<i32>(std::max<size_t>(bnd.size(), 1));
+        if (!bnd.empty()) EIG_HIP(hipMemcpy(A.march_bnd, bnd.data(), bnd.size() * sizeof(i32), hipMemcpyHostToDevice));
       }
-    }
-    catch (...)
-    {
-      destroy_mat(A);
-      throw;
-    }
-    *out = A;
+    });
   });
 }
 

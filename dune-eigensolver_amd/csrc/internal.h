@@ -240,7 +240,7 @@ struct eig_mat_s {
   eigmi::i32 *st_delta = nullptr;   // 8 * nslices
   uint8_t *st_mask = nullptr;       // nslices * C
   eigmi::i64 n_stencil_slices = 0;
-  // Symmetric band image (1x1 blocks, R = 1; api.cpp build_sym): when every row draws its columns
+  // Symmetric band image (1x1 blocks, R = 1; mat_image.cpp build_sym_image): when every row draws its columns
   // from one global set of at most kSymMaxOff offsets d = col - row and every stored pair
   // (r, r+d) / (r+d, r) is bitwise equal, the values live once, in nup = |{|d|}| window-indexed
   // arrays: sym_val[j * sym_ld + x] = a(x, x + p_j) = a(x + p_j, x) for the j-th non-negative
@@ -267,7 +267,7 @@ struct eig_mat_s {
   // bands: the value march streams the band arrays, k_spmv.hip march variant 10)
   bool sym_geo = false;
   int sym_gx = 0, sym_gy = 0, sym_gz = 0, sym_gz0 = 0;  // grid (global planes) and this rank's first plane
-  // Box-geometric masks (api.cpp build_sym): offsets inside the 27-point box a D + b nx + c (a, b, c in
+  // Box-geometric masks (mat_image.cpp build_sym_image): offsets inside the 27-point box a D + b nx + c (a, b, c in
   // {-1, 0, 1}) of an nx x ny x nz grid, every row storing exactly its in-grid neighbours among them
   // (sym_geo's 5 / 7-point grids excluded); sym_box27 = bit (a + 1) 9 + (b + 1) 3 + (c + 1) per stored
   // offset; grid in sym_gx / gy / gz / gz0.  The box marches (k_spmv.hip, e.g. the P1 Kuhn 15-point

@@ -296,7 +296,7 @@ __device__ __forceinline__ void sym_span(const SymImg &S, int kb, int ke, unsign
 
 // Row r (window index w = own + r) of the symmetric band image, one row per lane; a row sums
 // exactly its stored entries in ascending-column order (bitwise BCRSMatrix::mv when the matrix is
-// bitwise symmetric, which build_sym checks).  `centre` returns the row's own operand x[w] (the
+// bitwise symmetric, which mat_image.cpp build_sym_image checks).  `centre` returns the row's own operand x[w] (the
 // fused step takes its (t, u) from it).
 // NEAR: the offsets -1 / 0 / +1 share one centre load -- the neighbours' operands and the
 // mirrored -1 value come from the adjacent lanes by DPP lane shifts (lanes 0 / 63 load theirs):

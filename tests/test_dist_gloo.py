@@ -144,7 +144,7 @@ def _worker(rank, world, port, N, steps, q, variant="classic"):
         dist.all_gather(allr, mine)
         ranks = torch.stack(allr).numpy()
         recvs, sends = eigmi.plan_halo(world, rank, ranks, wb)
-        cl = (c[:rp[-1]] - wb).astype(np.int32)  # window-local columns, as build_sell stores them
+        cl = (c[:rp[-1]] - wb).astype(np.int32)  # window-local columns, as build_sell_image stores them
         assert cl.min() >= 0 and cl.max() < wlen
 
         def halo(x):

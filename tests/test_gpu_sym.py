@@ -1,4 +1,4 @@
-"""GPU parity of the symmetric band image (internal.h eig_mat_s::sym_*, api.cpp build_sym).
+"""GPU parity of the symmetric band image (internal.h eig_mat_s::sym_*, mat_image.cpp build_sym_image).
 
 A square 1x1 matrix whose rows draw their columns from at most 32 offsets and whose stored mirror
 pairs are bitwise equal keeps its values once, in upper-triangle band arrays; the scalar SpMV and
