@@ -15,6 +15,7 @@ import scipy.sparse as sp
 
 import eigmi
 import oracle
+from lu_factors import BINV_RTOL  # 1e-13 of max |result|: the block-inverse solve's bound, shared
 
 
 def factors(A):
@@ -115,11 +116,6 @@ class trsv_kernel:
 
     def __exit__(self, *a):
         self.lu.set_solver(None)
-
-
-# The block-inverse solve multiplies by inv(D_b) instead of substituting: agreement with the
-# reference arithmetic to rounding.  Bound: 1e-13 of the largest |entry| of the result.
-BINV_RTOL = 1e-13
 
 
 @pytest.mark.gpu
@@ -269,10 +265,12 @@ def test_generalized_inverse_pu_mass(ctx):
                                   "poisson3d_20", "laplace2d_200"])
 @pytest.mark.parametrize("kernel", ["staged", "csr", None])
 def test_inverse_mv8_kernels(ctx, name, kernel):
-    """The bitwise triangular-solve kernels (k_tsolve_staged: envelope factors of bandwidth <= 256;
-    k_tsolve: any factor) reproduce the reference arithmetic bitwise; the default block-inverse
-    solve (factors that fit the staged image) to BINV_RTOL.  poisson3d_20's RCM envelope reaches
-    past 256 rows: it always takes k_tsolve.  laplace2d_100: n = 10000, a ragged last block.  The
+    """The row-CSR substitution kernel k_tsolve reproduces the reference arithmetic bitwise; the
+    default block-inverse solve to BINV_RTOL.  Every factor here has a block-inverse image, and
+    beside one "staged" selects k_tsolve as "csr" does (the staged image is built only for factors
+    without a block-inverse image): both parameters run k_tsolve, and the printed kernel name says
+    so.  k_tsolve_staged itself is reached in tests/test_gpu_trsv_factors.py.  poisson3d_20's RCM
+    envelope reaches past 256 rows.  laplace2d_100: n = 10000, a ragged last block.  The
     block-inverse chain's coupled-block counts: laplace2d_64 1, laplace2d_100 / poisson3d_12 2,
     poisson3d_16 4 (RCM bandwidth 200).  The block-inverse chain is independent of the staged image
     (coupled distances 3 and up to 8 compared with the reference arithmetic):
@@ -289,6 +287,7 @@ def test_inverse_mv8_kernels(ctx, name, kernel):
     X = oracle.random_mv8(A.n, 16, 3)
     ref_out, _ = oracle.inverse_mv8(f, X, 16)
     with trsv_kernel(lu, kernel):
+        print(f"{name}: solver {kernel} runs kernel {lu.solver_info()[0]}")
         din, dout = ctx.array(X), ctx.zeros(A.n * 16)
         lu.inverse_mv8(16, din, dout)
     out = dout.get()
