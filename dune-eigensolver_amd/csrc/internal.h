@@ -591,9 +591,9 @@ struct TrsvImage {
   bool rows = false;                      // the row-CSR factors are on the device
   hipStream_t stream = nullptr;           // the owning context's stream (uploads)
   // Block-staged image (k_tsolve_staged, k_trsv.hip), per factor (0 = L, 1 = U) and 64-row block b:
-  // the entries outside the block as an ELL slab [k][r] (off1[b] .. + w1[b] * 64; column -1 =
-  // padding), the entries inside it as a dense 64 x 64 tile [t][r] (tile + b * 4096) + row masks.
-  i64 *off1[2] = {nullptr, nullptr};
+  // the entries outside the block as an ELL slab [k][r] (w1[b] columns of 64 from b * kSlab * 64; column
+  // -1 = padding), the entries inside it as a dense 64 x 64 tile [t][r] (tile + b * 4096) + row masks
+  // (trsv_image.h build_staged_image).
   i32 *w1[2] = {nullptr, nullptr};
   double *v1[2] = {nullptr, nullptr};
   i32 *c1[2] = {nullptr, nullptr};
@@ -602,9 +602,9 @@ struct TrsvImage {
   bool staged = false;  // the factors fit k_tsolve_staged (k_trsv.hip)
   int solver = 0;       // eig_lu_set_solver: EIG_TRSV_AUTO / _BLOCKINV / _STAGED / _CSR
   // the staged image is built on first use (EIG_TRSV_STAGED, or factors without the
-  // block-inverse image): host copies of the split factor rows until then
+  // block-inverse image): host copies of the factor rows and their splits (trsv_image.h) until then
   bool staged_built = false;
-  std::shared_ptr<struct TrsvHostRows> host;
+  std::shared_ptr<struct TrsvHost> host;
   // Block-inverse image (k_binv_z / k_binv_chain, k_trsv.hip), per factor: the inverse of every
   // 64 x 64 diagonal block, dinv + b * 4096 as [t][r], and G(b, d) = inv(D_b) T(b, d) for the
   // coupling T(b, d) of block b to the block d before it (L) / after it (U), g + (b * gd + d - 1) * 4096
@@ -613,13 +613,10 @@ struct TrsvImage {
   int gd[2] = {0, 0};
   bool binv = false;
 };
-void trsv_upload_rows(TrsvImage &img, const std::vector<i64> &lrp, const std::vector<i32> &lc,
-                      const std::vector<double> &lv, const std::vector<i64> &urp, const std::vector<i32> &uc,
-                      const std::vector<double> &uv, const std::vector<double> &ud);
-void trsv_upload(eig_ctx_t ctx, i64 n, const std::vector<i64> &lrp, const std::vector<i32> &lc,
-                 const std::vector<double> &lv, const std::vector<i64> &urp, const std::vector<i32> &uc,
-                 const std::vector<double> &uv, const std::vector<double> &ud, const std::vector<i64> &P,
-                 const std::vector<i64> &Q, const std::vector<double> &scale, TrsvImage &img);
+struct FactorRows;  // trsv_image.h
+void trsv_upload_rows(TrsvImage &img, const FactorRows &rows);
+void trsv_upload(eig_ctx_t ctx, i64 n, const FactorRows &rows, const std::vector<i64> &P, const std::vector<i64> &Q,
+                 const std::vector<double> &scale, TrsvImage &img);
 void trsv_free(TrsvImage &img);
 void trsv_attach_perm(eig_ctx_t ctx, i64 n, const std::vector<i64> &P, const std::vector<i64> &Q,
                       const std::vector<double> &scale, TrsvImage &img);

@@ -20,6 +20,7 @@
 // and G tiles.  The host envelope LU plus the host image builder were ~70 % of a 200^2 setup
 // (n bw^2 multiply-adds each, on host cores); here they are ~2 nb + 2 short launches.
 #include "internal.h"
+#include "trsv_image.h"
 
 #include <chrono>
 #include <cstdio>
@@ -360,7 +361,7 @@ bool band_lu_device(eig_ctx_t ctx, i64 n, int gd, const std::vector<i64> &rp, co
     }
     phase("factor");
     hipLaunchKernelGGL(k_band_tinv, dim3((unsigned)nb, 2), dim3(64), 0, s, gd, (const double *)band, dl, du, flags,
-                       1e6);
+                       kBinvCond);
     if (gd > 0)
       hipLaunchKernelGGL(k_band_g, dim3((unsigned)nb, gd, 2), dim3(256), 0, s, gd, (const double *)band,
                          (const double *)dl, (const double *)du, gl, gu);

@@ -20,18 +20,18 @@
 // workgroup after a __syncthreads (workgroup-scope ordering).
 // Default where the factor fits the staged image: the block-inverse solve (k_binv_z +
 // k_binv_chain below; to rounding, not bitwise); EIGMI_TRSV=staged / csr keep the bitwise kernels.
+// The host images (row splits, admission, block-inverse tiles, staged slabs) are built by
+// trsv_image.cpp; this file uploads them and solves.
 #include "internal.h"
+#include "trsv_image.h"
 
-#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <cstdio>
-#include <thread>
 
 namespace eigmi {
 
 namespace {
-constexpr int kTB = 64;       // rows per block
 constexpr int kTThreads = 512;  // 8 waves = the 8 columns of a column block
 constexpr int kRing = 3;        // solved blocks whose x stays in LDS for phase 1
 constexpr int kThreadsT = kTThreads;
@@ -198,19 +198,8 @@ __global__ __launch_bounds__(kTThreads) void k_tsolve(i64 n, const i64 *__restri
 // 512 threads load block b+1's ELL slab of outside-the-block entries ([k][r]: 64 rows per
 // instruction) and its dense in-block tile into registers during block b's register wavefront; at
 // staging the columns become ring indices, so phase 1 is LDS reads and selected subtractions
-// without per-entry branches.
-constexpr int kRing4 = 4;   // ring slots of the staged kernel (power of two)
-constexpr int kSlab = 128;  // slab entries per row staged at once (LDS: 96 KiB of slab + 32 KiB tile)
-// block-inverse image: at most kBinvMaxGD coupled blocks per factor (envelope bandwidth <= 512 rows)
-// and kBinvTiles 64 x 64 double tiles for both factors (1 GiB); a diagonal block whose estimated
-// condition max|D_b| max|inv(D_b)| 64 exceeds kBinvCond keeps the factors on the substitution
-// kernels (products with an inverse of an ill-conditioned block lose what substitution keeps)
-constexpr int kBinvMaxGD = 8;
-constexpr i64 kBinvTiles = 32768;
-constexpr double kBinvCond = 1e6;
-
+// without per-entry branches.  (kSlab, kRing4 and the image layout: trsv_image.h.)
 struct Staged {
-  const i64 *off1;
   const i32 *w1;
   const double *v1;
   const i32 *c1;
@@ -677,111 +666,25 @@ T *upload(const std::vector<T> &h, hipStream_t stream)
   }
   return static_cast<T *>(p);
 }
-}  // namespace
 
-struct TrsvHostRows {
-  std::vector<i64> lrp;
-  std::vector<i32> lc;
-  std::vector<double> lv;
-  std::vector<i64> ls, urp;
-  std::vector<i32> uc;
-  std::vector<double> uv;
-  std::vector<i64> us;
-};
-
-namespace {
 // Build the block-staged images (k_tsolve_staged) from the host rows kept at upload.
 void build_staged(TrsvImage &img)
 {
-  const i64 n = img.n;
-  const TrsvHostRows &H = *img.host;
-  // block-staged images (k_tsolve_staged): per 64-row block, the outside-the-block entries of each
-  // row as an ELL slab [k][r] in the row's own order, the inside entries as a dense tile [t][r]
+  const FactorRows &R = img.host->rows;
+  const RowSplits &S = img.host->splits;
   auto stage = [&](int f, const std::vector<i64> &rp, const std::vector<i32> &cj, const std::vector<double> &cv,
                    const std::vector<i64> &split) {
-    // slab: the first kSlab entries of every row at a fixed place (block b: b * kSlab * 64), the
-    // rest (rows wider than kSlab) in an overflow slab at off[b]
-    const i64 nblocks = (n + kTB - 1) / kTB;
-    std::vector<i64> off(nblocks + 1, 0);
-    std::vector<i32> w(std::max<i64>(nblocks, 1), 0);
-    const i64 fixed = nblocks * kSlab * kTB;
-    for (i64 b = 0; b < nblocks; ++b)
-    {
-      i64 mw = 0;
-      for (i64 i = b * kTB; i < std::min(n, b * kTB + kTB); ++i) mw = std::max(mw, split[i] - rp[i]);
-      w[b] = (i32)mw;
-      off[b + 1] = off[b] + std::max<i64>(mw - kSlab, 0) * kTB;
-    }
-    for (i64 b = 0; b <= nblocks; ++b) off[b] += fixed;
-    std::vector<double> v1(std::max<i64>(off[nblocks], 1), 0.0);
-    std::vector<i32> c1(std::max<i64>(off[nblocks], 1), -1);
-    std::vector<double> tl((size_t)std::max<i64>(nblocks, 1) * kTB * kTB, 0.0);
-    std::vector<unsigned long long> tm((size_t)std::max<i64>(nblocks, 1) * kTB, 0ull);
-    for (i64 b = 0; b < nblocks; ++b)
-      for (i64 i = b * kTB; i < std::min(n, b * kTB + kTB); ++i)
-      {
-        const i64 r = i - b * kTB;
-        for (i64 q = rp[i]; q < split[i]; ++q)
-        {
-          const i64 k = q - rp[i];
-          const i64 at = k < kSlab ? (b * kSlab + k) * kTB + r : off[b] + (k - kSlab) * kTB + r;
-          v1[at] = cv[q];
-          c1[at] = cj[q];
-        }
-        for (i64 q = split[i]; q < rp[i + 1]; ++q)
-        {
-          const i64 t = cj[q] - b * kTB;
-          tl[(size_t)b * kTB * kTB + t * kTB + r] = cv[q];
-          tm[(size_t)b * kTB + r] |= 1ull << t;
-        }
-      }
-    off.resize(nblocks);
-    img.off1[f] = upload(off, img.stream);
-    img.w1[f] = upload(w, img.stream);
-    img.v1[f] = upload(v1, img.stream);
-    img.c1[f] = upload(c1, img.stream);
-    img.tile[f] = upload(tl, img.stream);
-    img.tmask[f] = upload(tm, img.stream);
+    const StagedImage h = build_staged_image(img.n, rp, cj, cv, split);
+    img.w1[f] = upload(h.w, img.stream);
+    img.v1[f] = upload(h.v1, img.stream);
+    img.c1[f] = upload(h.c1, img.stream);
+    img.tile[f] = upload(h.tile, img.stream);
+    img.tmask[f] = upload(h.tmask, img.stream);
   };
-  stage(0, H.lrp, H.lc, H.lv, H.ls);
-  stage(1, H.urp, H.uc, H.uv, H.us);
+  stage(0, R.lrp, R.lc, R.lv, S.ls);
+  stage(1, R.urp, R.uc, R.uv, S.us);
   img.staged_built = true;
   img.host.reset();
-}
-}  // namespace
-
-namespace {
-// f(b0, b1) over contiguous block ranges on up to 16 host threads
-template <class F>
-void parallel_blocks(i64 nb, F &&f)
-{
-  unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (nb < 32) nt = 1;
-  if (nt == 1) return f(0, nb);
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; ++t) th.emplace_back([&, t] { f(nb * t / nt, nb * (t + 1) / nt); });
-  for (auto &t : th) t.join();
-}
-}  // namespace
-
-namespace {
-// split points: L row i -> first entry inside i's 64-row block; U row i (descending columns) ->
-// first entry with a column inside the block
-void row_splits(i64 n, const std::vector<i64> &lrp, const std::vector<i32> &lc, const std::vector<i64> &urp,
-                const std::vector<i32> &uc, std::vector<i64> &ls, std::vector<i64> &us)
-{
-  ls.resize(n);
-  us.resize(n);
-  for (i64 i = 0; i < n; ++i)
-  {
-    const i64 bs = i / kTB * kTB, be = std::min(bs + kTB, n);
-    i64 k = lrp[i];
-    while (k < lrp[i + 1] && lc[k] < bs) ++k;
-    ls[i] = k;
-    k = urp[i];
-    while (k < urp[i + 1] && uc[k] >= be) ++k;
-    us[i] = k;
-  }
 }
 
 // Host arrays into ONE device allocation with ONE copy (a dozen separate small hipMalloc + hipMemcpy
@@ -815,20 +718,32 @@ void *upload_parts(const std::vector<std::pair<const void *, size_t>> &parts, st
   for (size_t k = 0; k < parts.size(); ++k) at[k] = static_cast<char *>(d) + off[k];
   return d;
 }
+
+// The permutations (narrowed to i32) and the scaling every solve applies.
+void upload_perm(const std::vector<i64> &P, const std::vector<i64> &Q, const std::vector<double> &scale,
+                 TrsvImage &img)
+{
+  std::vector<i32> p32(P.begin(), P.end()), q32(Q.begin(), Q.end());
+  std::vector<char *> at;
+  img.arena = upload_parts({{p32.data(), p32.size() * 4}, {q32.data(), q32.size() * 4}, {scale.data(), scale.size() * 8}},
+                           at, img.stream);
+  img.P = (i32 *)at[0];
+  img.Q = (i32 *)at[1];
+  img.scale = (double *)at[2];
+}
 }  // namespace
 
 // The row-CSR factors the substitution kernels read (k_tsolve, and the U diagonal of the staged one).
-void trsv_upload_rows(TrsvImage &img, const std::vector<i64> &lrp, const std::vector<i32> &lc,
-                      const std::vector<double> &lv, const std::vector<i64> &urp, const std::vector<i32> &uc,
-                      const std::vector<double> &uv, const std::vector<double> &ud)
+void trsv_upload_rows(TrsvImage &img, const FactorRows &R)
 {
   if (img.rows) return;
-  std::vector<i64> ls, us;
-  row_splits(img.n, lrp, lc, urp, uc, ls, us);
+  const RowSplits S = row_splits(img.n, R);
   std::vector<char *> at;
-  img.arena_rows = upload_parts({{lrp.data(), lrp.size() * 8}, {ls.data(), ls.size() * 8}, {lc.data(), lc.size() * 4},
-                                 {lv.data(), lv.size() * 8}, {urp.data(), urp.size() * 8}, {us.data(), us.size() * 8},
-                                 {uc.data(), uc.size() * 4}, {uv.data(), uv.size() * 8}, {ud.data(), ud.size() * 8}},
+  img.arena_rows = upload_parts({{R.lrp.data(), R.lrp.size() * 8}, {S.ls.data(), S.ls.size() * 8},
+                                 {R.lc.data(), R.lc.size() * 4}, {R.lv.data(), R.lv.size() * 8},
+                                 {R.urp.data(), R.urp.size() * 8}, {S.us.data(), S.us.size() * 8},
+                                 {R.uc.data(), R.uc.size() * 4}, {R.uv.data(), R.uv.size() * 8},
+                                 {R.ud.data(), R.ud.size() * 8}},
                                 at, img.stream);
   img.lrp = (i64 *)at[0];
   img.lsplit = (i64 *)at[1];
@@ -842,10 +757,8 @@ void trsv_upload_rows(TrsvImage &img, const std::vector<i64> &lrp, const std::ve
   img.rows = true;
 }
 
-void trsv_upload(eig_ctx_t ctx, i64 n, const std::vector<i64> &lrp, const std::vector<i32> &lc,
-                 const std::vector<double> &lv, const std::vector<i64> &urp, const std::vector<i32> &uc,
-                 const std::vector<double> &uv, const std::vector<double> &ud, const std::vector<i64> &P,
-                 const std::vector<i64> &Q, const std::vector<double> &scale, TrsvImage &img)
+void trsv_upload(eig_ctx_t ctx, i64 n, const FactorRows &R, const std::vector<i64> &P, const std::vector<i64> &Q,
+                 const std::vector<double> &scale, TrsvImage &img)
 {
   img.n = n;
   img.stream = ctx ? ctx->stream : nullptr;
@@ -858,168 +771,44 @@ void trsv_upload(eig_ctx_t ctx, i64 n, const std::vector<i64> &lrp, const std::v
     fprintf(stderr, "trsv_upload %-10s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
   };
-  std::vector<i64> ls, us;
-  row_splits(n, lrp, lc, urp, uc, ls, us);
-  std::vector<i32> p32(n), q32(n);
-  for (i64 k = 0; k < n; ++k)
-  {
-    p32[k] = (i32)P[k];
-    q32[k] = (i32)Q[k];
-  }
-  // admission to the staged kernel: <= kSlab outside entries per row, all within kRing4 blocks
-  auto fits = [&](const std::vector<i64> &rp, const std::vector<i32> &cj, const std::vector<i64> &split, bool lower) {
-    for (i64 i = 0; i < n; ++i)
-    {
-      if (split[i] - rp[i] > kSlab) return false;
-      const i64 blk = i / kTB;
-      for (i64 q = rp[i]; q < split[i]; ++q)
-      {
-        const i64 cb = cj[q] / kTB;
-        if (lower ? (cb < blk - kRing4) : (cb > blk + kRing4)) return false;
-      }
-    }
-    return true;
-  };
+  const RowSplits S = row_splits(n, R);
   phase("split");
-  img.staged = fits(lrp, lc, ls, true) && fits(urp, uc, us, false);
+  const TrsvPlan plan = trsv_plan(n, R, S);
+  img.staged = plan.staged;
+  img.gd[0] = plan.gd[0];
+  img.gd[1] = plan.gd[1];
   phase("staged");
-  // block-inverse images (k_binv_z / k_binv_chain) for factors whose every coupling lies within
-  // kBinvMaxGD blocks, when the tiles stay within kBinvTiles (a 64 x 64 tile per diagonal block and
-  // per coupled block) and every diagonal block is well conditioned
-  const i64 nblocks = (n + kTB - 1) / kTB;
-  auto coupled = [&](const std::vector<i64> &rp, const std::vector<i32> &cj, const std::vector<i64> &split,
-                     bool lower) {
-    int dm = 0;
-    for (i64 i = 0; i < n; ++i)
-      for (i64 q = rp[i]; q < split[i]; ++q)
-        dm = std::max<int>(dm, (int)(lower ? i / kTB - cj[q] / kTB : cj[q] / kTB - i / kTB));
-    return dm;
-  };
-  // returns false (nothing uploaded) when a diagonal block fails the conditioning test
+  // block-inverse images (k_binv_z / k_binv_chain) where the plan admits them and every diagonal
+  // block is well conditioned: one factor's tiles built, uploaded and released before the next's
   auto binv_image = [&](int f, const std::vector<i64> &rp, const std::vector<i32> &cj, const std::vector<double> &cv,
-                        const std::vector<i64> &split, const double *diag) -> bool {
-    const bool lower = diag == nullptr;
-    const int gd = img.gd[f];
-    const size_t T2 = (size_t)kTB * kTB;
-    std::vector<double> dinv((size_t)nblocks * T2, 0.0), gt((size_t)std::max<i64>(nblocks * gd, 1) * T2, 0.0);
-    std::atomic<bool> ok{true};
-    // blocks are independent: threads over contiguous block ranges
-    parallel_blocks(nblocks, [&](i64 b0, i64 b1) {
-    // Di holds inv(D_b) by columns (Di[j * 64 + i] = inv(D)[i][j]): each column is one triangular
-    // solve with contiguous operands, and it is already the device layout of dinv ([t][r])
-    std::vector<double> Db(T2), Di(T2), Tb(T2);
-    for (i64 b = b0; b < b1 && ok.load(std::memory_order_relaxed); ++b)
-    {
-      const i64 bs = b * kTB, nbr = std::min<i64>(kTB, n - bs);
-      // the diagonal block D[r][t] (rows past n: identity)
-      std::fill(Db.begin(), Db.end(), 0.0);
-      for (int r = 0; r < kTB; ++r) Db[r * kTB + r] = (r < nbr && !lower) ? diag[bs + r] : 1.0;
-      for (i64 r = 0; r < nbr; ++r)
-        for (i64 q = split[bs + r]; q < rp[bs + r + 1]; ++q) Db[r * kTB + (cj[q] - bs)] = cv[q];
-      // its inverse, column j = the solution of D x = e_j (lower: top-down, upper: bottom-up)
-      std::fill(Di.begin(), Di.end(), 0.0);
-      for (int j = 0; j < kTB; ++j)
-      {
-        double *x = &Di[(size_t)j * kTB];
-        if (lower)
-          for (int i = j; i < kTB; ++i)
-          {
-            const double *Dr = &Db[(size_t)i * kTB];
-            double v = i == j ? 1.0 : 0.0;
-            for (int k = j; k < i; ++k) v -= Dr[k] * x[k];
-            x[i] = v / Dr[i];
-          }
-        else
-          for (int i = j; i >= 0; --i)
-          {
-            const double *Dr = &Db[(size_t)i * kTB];
-            double v = i == j ? 1.0 : 0.0;
-            for (int k = i + 1; k <= j; ++k) v -= Dr[k] * x[k];
-            x[i] = v / Dr[i];
-          }
-      }
-      {
-        double dm = 0.0, im = 0.0;
-        for (size_t q = 0; q < T2; ++q)
-        {
-          dm = std::max(dm, std::fabs(Db[q]));
-          im = std::max(im, std::fabs(Di[q]));
-        }
-        if (!(dm * im * kTB <= kBinvCond)) ok = false;  // (NaN included)
-      }
-      std::copy(Di.begin(), Di.end(), dinv.begin() + (size_t)b * T2);
-      // G(b, d) = inv(D_b) T(b, d), T(b, d)[r'][t] = the entry of row bs + r' in column t of block b -+ d
-      for (int d = 1; d <= gd; ++d)
-      {
-        const i64 src = lower ? b - d : b + d;
-        if (src < 0 || src >= nblocks) continue;
-        std::fill(Tb.begin(), Tb.end(), 0.0);
-        bool any = false;
-        for (i64 r = 0; r < nbr; ++r)
-          for (i64 q = rp[bs + r]; q < split[bs + r]; ++q)
-            if (cj[q] / kTB == src)
-            {
-              Tb[r * kTB + (cj[q] - src * kTB)] += cv[q];
-              any = true;
-            }
-        if (!any) continue;
-        double *gb = &gt[((size_t)b * gd + (d - 1)) * T2];
-        for (int rr = 0; rr < kTB; ++rr)  // G[:, t] += inv(D)[:, rr] T[rr][t] (column rr of inv(D):
-        {                                 // rows rr.. (lower) / ..rr (upper) are its nonzeros)
-          const double *dcol = &Di[(size_t)rr * kTB];
-          const int r0 = lower ? rr : 0, r1 = lower ? kTB : rr + 1;
-          for (int t = 0; t < kTB; ++t)
-          {
-            const double tv = Tb[rr * kTB + t];
-            if (tv == 0.0) continue;
-            double *gcol = gb + (size_t)t * kTB;
-            for (int r = r0; r < r1; ++r) gcol[r] += dcol[r] * tv;
-          }
-        }
-      }
-    }
-    });
-    if (!ok) return false;
-    img.dinv[f] = upload(dinv, img.stream);
-    img.g[f] = upload(gt, img.stream);
+                        const std::vector<i64> &split, const double *diag) {
+    const BinvTiles t = build_binv_tiles(n, rp, cj, cv, split, diag, img.gd[f]);
+    if (!t.ok) return false;
+    img.dinv[f] = upload(t.dinv, img.stream);
+    img.g[f] = upload(t.g, img.stream);
     return true;
   };
+  img.binv = plan.binv_admitted;
+  if (img.binv)
   {
-    img.gd[0] = coupled(lrp, lc, ls, true);
-    img.gd[1] = coupled(urp, uc, us, false);
-    const i64 tiles = nblocks * (2 + img.gd[0] + img.gd[1]);
-    bool pivots = true;  // a zero U pivot leaves the reference's division to produce inf / nan
-    for (i64 i = 0; i < n; ++i) pivots = pivots && ud[i] != 0.0;
-    img.binv = pivots && tiles <= kBinvTiles && img.gd[0] <= kBinvMaxGD && img.gd[1] <= kBinvMaxGD;
-    if (img.binv)
-    {
-      img.binv = binv_image(0, lrp, lc, lv, ls, nullptr) && binv_image(1, urp, uc, uv, us, ud.data());
-      if (!img.binv)
-        for (int f = 0; f < 2; ++f)
-        {
-          if (img.dinv[f]) (void)hipFree(img.dinv[f]);
-          if (img.g[f]) (void)hipFree(img.g[f]);
-          img.dinv[f] = img.g[f] = nullptr;
-        }
-    }
+    img.binv = binv_image(0, R.lrp, R.lc, R.lv, S.ls, nullptr) && binv_image(1, R.urp, R.uc, R.uv, S.us, R.ud.data());
+    if (!img.binv)
+      for (int f = 0; f < 2; ++f)
+      {
+        if (img.dinv[f]) (void)hipFree(img.dinv[f]);
+        if (img.g[f]) (void)hipFree(img.g[f]);
+        img.dinv[f] = img.g[f] = nullptr;
+      }
   }
   // host rows for a later build of the staged image: only when the staged kernel is the default
   // (no block-inverse image); with one, EIG_TRSV_STAGED takes the row-CSR kernel (bitwise too)
-  if (img.staged && !img.binv)
-    img.host = std::make_shared<TrsvHostRows>(TrsvHostRows{lrp, lc, lv, ls, urp, uc, uv, us});
+  if (img.staged && !img.binv) img.host = std::make_shared<TrsvHost>(TrsvHost{R, S});
   phase("binv");
   // permutations and scaling (every solve); the row-CSR factors only where a substitution kernel
   // is the default -- with the block-inverse image they are uploaded when eig_lu_set_solver asks
   // for EIG_TRSV_STAGED / _CSR (lu.cpp rebuilds them from the factors it keeps)
-  {
-    std::vector<char *> at;
-    img.arena = upload_parts({{p32.data(), p32.size() * 4}, {q32.data(), q32.size() * 4},
-                              {scale.data(), scale.size() * 8}}, at, img.stream);
-    img.P = (i32 *)at[0];
-    img.Q = (i32 *)at[1];
-    img.scale = (double *)at[2];
-  }
-  if (!img.binv) trsv_upload_rows(img, lrp, lc, lv, urp, uc, uv, ud);
+  upload_perm(P, Q, scale, img);
+  if (!img.binv) trsv_upload_rows(img, R);
   phase("csr");
 }
 
@@ -1030,24 +819,13 @@ void trsv_attach_perm(eig_ctx_t ctx, i64 n, const std::vector<i64> &P, const std
 {
   img.n = n;
   img.stream = ctx->stream;
-  std::vector<i32> p32(n), q32(n);
-  for (i64 k = 0; k < n; ++k)
-  {
-    p32[k] = (i32)P[k];
-    q32[k] = (i32)Q[k];
-  }
-  std::vector<char *> at;
-  img.arena = upload_parts({{p32.data(), p32.size() * 4}, {q32.data(), q32.size() * 4}, {scale.data(), scale.size() * 8}},
-                           at, img.stream);
-  img.P = (i32 *)at[0];
-  img.Q = (i32 *)at[1];
-  img.scale = (double *)at[2];
+  upload_perm(P, Q, scale, img);
 }
 
 void trsv_free(TrsvImage &img)
 {
   for (int f = 0; f < 2; ++f)
-    for (void *p : {(void *)img.off1[f], (void *)img.w1[f], (void *)img.v1[f], (void *)img.c1[f], (void *)img.tile[f],
+    for (void *p : {(void *)img.w1[f], (void *)img.v1[f], (void *)img.c1[f], (void *)img.tile[f],
                     (void *)img.tmask[f], (void *)img.dinv[f], (void *)img.g[f]})
       if (p) (void)hipFree(p);
   if (img.arena) (void)hipFree(img.arena);
@@ -1091,8 +869,8 @@ void launch_inverse_mv8(TrsvImage &img, i64 m, double *Qin, double *Qout, hipStr
   }
   else
   {
-    const Staged L{img.off1[0], img.w1[0], img.v1[0], img.c1[0], img.tile[0], img.tmask[0]};
-    const Staged U{img.off1[1], img.w1[1], img.v1[1], img.c1[1], img.tile[1], img.tmask[1]};
+    const Staged L{img.w1[0], img.v1[0], img.c1[0], img.tile[0], img.tmask[0]};
+    const Staged U{img.w1[1], img.v1[1], img.c1[1], img.tile[1], img.tmask[1]};
     hipLaunchKernelGGL(k_tsolve_staged<true>, dim3(nblk), dim3(kTThreads), 0, s, n, L, (const double *)nullptr,
                        (const double *)Qout, Qin);
     hipLaunchKernelGGL(k_tsolve_staged<false>, dim3(nblk), dim3(kTThreads), 0, s, n, U, (const double *)img.ud,

@@ -23,14 +23,14 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "trsv_image.h"
 
 using namespace eigmi;
 
 namespace {
 
-// device band factorisation admission: coupled 64-row blocks (the block-inverse chain's limit) and
-// band + image tiles (2 GiB of 64 x 64 double tiles)
-constexpr i64 kBandMaxGD = 8;
+// device band factorisation admission: at most kBinvMaxGD coupled 64-row blocks (the block-inverse
+// chain's limit) and band + image tiles (2 GiB of 64 x 64 double tiles)
 constexpr i64 kBandMaxTiles = 65536;
 
 // Reverse Cuthill-McKee on the symmetrised pattern; per connected component a BFS from a
@@ -137,8 +137,9 @@ struct eig_lu_s {
   i64 n = 0;
   int do_recip = 0;
   // host copy of the factors in the exported (UMFPACK) form
-  std::vector<i64> Lp, Lj, Up, Ui, P, Q;
-  std::vector<double> Lx, Ux, Rs;
+  ExportedFactors ex;
+  std::vector<i64> P, Q;
+  std::vector<double> Rs;
   // device image (k_trsv.hip): L rows without the unit diagonal, ascending columns; U rows
   // (transposed from the columns) without the diagonal, DESCENDING columns; U diagonal
   TrsvImage img;
@@ -157,79 +158,10 @@ struct eig_lu_s {
 
 namespace {
 
-// The factors in the row form the device solves read: L rows without the unit diagonal (ascending
-// columns), U rows without the diagonal (descending columns) and the U diagonal.
-void factor_rows(const eig_lu_s &lu, std::vector<i64> &lrp, std::vector<i32> &lc, std::vector<double> &lv,
-                 std::vector<i64> &urp, std::vector<i32> &uc, std::vector<double> &uv, std::vector<double> &ud)
+// The row form the device solves read (trsv_image.h), from the exported factors lu keeps.
+FactorRows rows_of(const eig_lu_s &lu)
 {
-  const i64 n = lu.n;
-  // L rows: the reference subtracts entries Lp[i] .. Lp[i+1]-2 in stored order (the last entry is
-  // the unit diagonal, kernels_cpp.hh:716-722).  Stored order is kept when ascending; otherwise the
-  // row is sorted by column (then equal to the reference to rounding, not bitwise).
-  lrp.assign(n + 1, 0);
-  urp.assign(n + 1, 0);
-  lc.clear();
-  lv.clear();
-  ud.assign(n, 0.0);
-  // L: rows copied as stored when ascending (the usual case), else through a sorted copy
-  lc.reserve(lu.Lx.size());
-  lv.reserve(lu.Lx.size());
-  std::vector<std::pair<i64, double>> e;
-  for (i64 i = 0; i < n; ++i)
-  {
-    const i64 b = lu.Lp[i], t = lu.Lp[i + 1] - 1;  // (the last entry is the unit diagonal)
-    bool sorted = true;
-    for (i64 k = b; k < t; ++k)
-    {
-      EIG_CHECK(lu.Lj[k] >= 0 && lu.Lj[k] < i, EIG_ERR_ARG, "L factor: entry not strictly below the diagonal");
-      if (k > b && lu.Lj[k] < lu.Lj[k - 1]) sorted = false;
-    }
-    if (sorted)
-      for (i64 k = b; k < t; ++k)
-      {
-        lc.push_back((i32)lu.Lj[k]);
-        lv.push_back(lu.Lx[k]);
-      }
-    else
-    {
-      e.clear();
-      for (i64 k = b; k < t; ++k) e.push_back({lu.Lj[k], lu.Lx[k]});
-      std::stable_sort(e.begin(), e.end(), [](const auto &a, const auto &c) { return a.first < c.first; });
-      for (auto &q : e)
-      {
-        lc.push_back((i32)q.first);
-        lv.push_back(q.second);
-      }
-    }
-    lrp[i + 1] = (i64)lc.size();
-  }
-  // U: column j holds rows Ui[Up[j] .. Up[j+1]-2] above the diagonal Ux[Up[j+1]-1]; the reference's
-  // push loop (kernels_cpp.hh:730-745) updates row i with columns j in DECREASING order, which is
-  // the order the pull form below uses -- bitwise whatever the order inside a column.  Transposed
-  // by a counting sort over the columns in descending order (rows come out descending).
-  for (i64 j = 0; j < n; ++j)
-  {
-    EIG_CHECK(lu.Up[j + 1] > lu.Up[j], EIG_ERR_ARG, "U factor: empty column");
-    ud[j] = lu.Ux[lu.Up[j + 1] - 1];
-    for (i64 k = lu.Up[j]; k < lu.Up[j + 1] - 1; ++k)
-    {
-      EIG_CHECK(lu.Ui[k] >= 0 && lu.Ui[k] < j, EIG_ERR_ARG, "U factor: entry not strictly above the diagonal");
-      ++urp[lu.Ui[k] + 1];
-    }
-  }
-  for (i64 i = 0; i < n; ++i) urp[i + 1] += urp[i];
-  uc.resize((size_t)urp[n]);
-  uv.resize((size_t)urp[n]);
-  {
-    std::vector<i64> next(urp.begin(), urp.end() - 1);
-    for (i64 j = n - 1; j >= 0; --j)
-      for (i64 k = lu.Up[j]; k < lu.Up[j + 1] - 1; ++k)
-      {
-        const i64 at = next[lu.Ui[k]]++;
-        uc[at] = (i32)j;
-        uv[at] = lu.Ux[k];
-      }
-  }
+  return factor_rows(lu.n, lu.ex.Lp, lu.ex.Lj, lu.ex.Lx, lu.ex.Up, lu.ex.Ui, lu.ex.Ux);
 }
 
 // The exported form from the device band: L rows over the envelope [f_k, k) with the unit diagonal
@@ -245,63 +177,22 @@ void ensure_host(eig_lu_s &lu)
   EIG_HIP(hipStreamSynchronize(lu.ctx->stream));
   auto at = [&](i64 r, i64 c) { return h[((size_t)(r >> 6) * (2 * gd + 1) + ((c >> 6) - (r >> 6)) + gd) * 4096 +
                                          (size_t)(c & 63) * 64 + (r & 63)]; };
-  const std::vector<i64> &f = lu.f;
-  std::vector<i64> Lp(n + 1, 0), Up(n + 1, 0);
-  for (i64 k = 0; k < n; ++k)
-  {
-    i64 cl = 1, cu = 1;
-    for (i64 j = f[k]; j < k; ++j) cl += at(k, j) != 0.0;
-    for (i64 i = f[k]; i < k; ++i) cu += at(i, k) != 0.0;
-    Lp[k + 1] = Lp[k] + cl;
-    Up[k + 1] = Up[k] + cu;
-  }
-  std::vector<i64> Lj(Lp[n]), Ui(Up[n]);
-  std::vector<double> Lx(Lp[n]), Ux(Up[n]);
-  for (i64 k = 0; k < n; ++k)
-  {
-    i64 q = Lp[k];
-    for (i64 j = f[k]; j < k; ++j)
-      if (at(k, j) != 0.0)
-      {
-        Lj[q] = j;
-        Lx[q++] = at(k, j);
-      }
-    Lj[q] = k;
-    Lx[q] = 1.0;
-    q = Up[k];
-    for (i64 i = f[k]; i < k; ++i)
-      if (at(i, k) != 0.0)
-      {
-        Ui[q] = i;
-        Ux[q++] = at(i, k);
-      }
-    Ui[q] = k;
-    Ux[q] = at(k, k);
-  }
-  lu.Lp = std::move(Lp);
-  lu.Lj = std::move(Lj);
-  lu.Lx = std::move(Lx);
-  lu.Up = std::move(Up);
-  lu.Ui = std::move(Ui);
-  lu.Ux = std::move(Ux);
+  lu.ex = export_envelope(n, lu.f, at, at, [&](i64 k) { return at(k, k); });
   lu.host_ready = true;
 }
 
 void build_device(eig_lu_s &lu)
 {
   const i64 n = lu.n;
-  std::vector<i64> lrp, urp;
-  std::vector<i32> lc, uc;
-  std::vector<double> lv, uv, ud;
-  factor_rows(lu, lrp, lc, lv, urp, uc, uv, ud);
-  std::vector<i64> P(lu.P), Q(lu.Q);
+  const FactorRows rows = rows_of(lu);
+  const std::vector<i64> &P = lu.P, &Q = lu.Q;
   std::vector<double> scale(n);
   for (i64 k = 0; k < n; ++k)
   {
     EIG_CHECK(P[k] >= 0 && P[k] < n && Q[k] >= 0 && Q[k] < n, EIG_ERR_ARG, "permutation entry out of range");
     scale[k] = lu.do_recip ? lu.Rs[P[k]] : 1.0 / lu.Rs[P[k]];  // kernels_cpp.hh:683-705
   }
-  trsv_upload(lu.ctx, n, lrp, lc, lv, urp, uc, uv, ud, P, Q, scale, lu.img);
+  trsv_upload(lu.ctx, n, rows, P, Q, scale, lu.img);
 }
 
 }  // namespace
@@ -321,12 +212,12 @@ extern "C" int eig_lu_create(eig_ctx_t ctx, int64_t n, const int64_t *Lp, const 
       lu->ctx = ctx;
       lu->n = n;
       lu->do_recip = do_recip ? 1 : 0;
-      lu->Lp.assign(Lp, Lp + n + 1);
-      lu->Lj.assign(Lj, Lj + Lp[n]);
-      lu->Lx.assign(Lx, Lx + Lp[n]);
-      lu->Up.assign(Up, Up + n + 1);
-      lu->Ui.assign(Ui, Ui + Up[n]);
-      lu->Ux.assign(Ux, Ux + Up[n]);
+      lu->ex.Lp.assign(Lp, Lp + n + 1);
+      lu->ex.Lj.assign(Lj, Lj + Lp[n]);
+      lu->ex.Lx.assign(Lx, Lx + Lp[n]);
+      lu->ex.Up.assign(Up, Up + n + 1);
+      lu->ex.Ui.assign(Ui, Ui + Up[n]);
+      lu->ex.Ux.assign(Ux, Ux + Up[n]);
       lu->P.assign(P, P + n);
       lu->Q.assign(Q, Q + n);
       lu->Rs.assign(Rs, Rs + n);
@@ -448,14 +339,14 @@ extern "C" int eig_lu_create_bcsr(eig_ctx_t ctx, int64_t nb_rows, int br, const 
       for (i64 v : adj[perm[k]]) m = std::min(m, inv[v]);
       f[k] = m;
     }
-    // device factorisation (k_band.hip) when the envelope fits a band of at most kBandMaxGD coupled
+    // device factorisation (k_band.hip) when the envelope fits a band of at most kBinvMaxGD coupled
     // 64-row blocks: the band LU and the block-inverse image on the GPU, the exported form built
     // from the band only when asked for (eig_lu_info / _export / _set_solver staged or csr)
     {
       i64 gdm = 0;
       for (i64 k = 0; k < n; ++k) gdm = std::max(gdm, k / 64 - f[k] / 64);
       const i64 nb = (n + 63) / 64;
-      if (ctx && gdm <= kBandMaxGD && nb * (4 * gdm + 3) <= kBandMaxTiles)
+      if (ctx && gdm <= kBinvMaxGD && nb * (4 * gdm + 3) <= kBandMaxTiles)
       {
         std::vector<i64> rp(n + 1, 0);
         for (i64 i = 0; i < n; ++i) rp[i + 1] = rp[i] + (i64)rowsA[i].size();
@@ -552,38 +443,7 @@ extern "C" int eig_lu_create_bcsr(eig_ctx_t ctx, int64_t nb_rows, int br, const 
     }
     // exported form: L rows ascending + unit diagonal last; U columns ascending + diagonal last
     phase("factor");
-    std::vector<i64> Lp(n + 1, 0), Up(n + 1, 0);
-    for (i64 k = 0; k < n; ++k)
-    {
-      i64 cl = 1, cu = 1;  // + the unit / pivot diagonal
-      for (i64 j = f[k]; j < k; ++j) cl += Lat(k, j) != 0.0;
-      for (i64 i = f[k]; i < k; ++i) cu += Uat(i, k) != 0.0;
-      Lp[k + 1] = Lp[k] + cl;
-      Up[k + 1] = Up[k] + cu;
-    }
-    std::vector<i64> Lj(Lp[n]), Ui(Up[n]);
-    std::vector<double> Lx(Lp[n]), Ux(Up[n]);
-    for (i64 k = 0; k < n; ++k)
-    {
-      i64 q = Lp[k];
-      for (i64 j = f[k]; j < k; ++j)
-        if (Lat(k, j) != 0.0)
-        {
-          Lj[q] = j;
-          Lx[q++] = Lat(k, j);
-        }
-      Lj[q] = k;
-      Lx[q] = 1.0;
-      q = Up[k];
-      for (i64 i = f[k]; i < k; ++i)
-        if (Uat(i, k) != 0.0)
-        {
-          Ui[q] = i;
-          Ux[q++] = Uat(i, k);
-        }
-      Ui[q] = k;
-      Ux[q] = D[k];
-    }
+    ExportedFactors ex = export_envelope(n, f, Lat, Uat, [&](i64 k) { return D[k]; });
     phase("export");
     auto *lu = new eig_lu_s();
     try
@@ -591,12 +451,7 @@ extern "C" int eig_lu_create_bcsr(eig_ctx_t ctx, int64_t nb_rows, int br, const 
       lu->ctx = ctx;
       lu->n = n;
       lu->do_recip = 0;
-      lu->Lp = std::move(Lp);
-      lu->Lj = std::move(Lj);
-      lu->Lx = std::move(Lx);
-      lu->Up = std::move(Up);
-      lu->Ui = std::move(Ui);
-      lu->Ux = std::move(Ux);
+      lu->ex = std::move(ex);
       lu->P = perm;
       lu->Q = perm;
       lu->Rs = std::move(Rs);
@@ -618,8 +473,8 @@ extern "C" int eig_lu_info(eig_lu_t lu, int64_t *n, int64_t *lnz, int64_t *unz, 
     EIG_CHECK(lu, EIG_ERR_ARG, "eig_lu_info: null handle");
     ensure_host(*lu);
     if (n) *n = lu->n;
-    if (lnz) *lnz = lu->Lp[lu->n];
-    if (unz) *unz = lu->Up[lu->n];
+    if (lnz) *lnz = lu->ex.Lp[lu->n];
+    if (unz) *unz = lu->ex.Up[lu->n];
     if (do_recip) *do_recip = lu->do_recip;
   });
 }
@@ -636,11 +491,7 @@ extern "C" int eig_lu_set_solver(eig_lu_t lu, int kind)
       // the substitution kernels read the row factors, not uploaded next to a block-inverse image
       EIG_HIP(hipSetDevice(lu->ctx->device));
       ensure_host(*lu);
-      std::vector<i64> lrp, urp;
-      std::vector<i32> lc, uc;
-      std::vector<double> lv, uv, ud;
-      factor_rows(*lu, lrp, lc, lv, urp, uc, uv, ud);
-      trsv_upload_rows(lu->img, lrp, lc, lv, urp, uc, uv, ud);
+      trsv_upload_rows(lu->img, rows_of(*lu));
     }
     lu->img.solver = kind;
   });
@@ -667,12 +518,12 @@ extern "C" int eig_lu_export(eig_lu_t lu, int64_t *Lp, int64_t *Lj, double *Lx, 
   return guard(lu ? lu->ctx : nullptr, [&] {
     EIG_CHECK(lu && Lp && Lj && Lx && Up && Ui && Ux && P && Q && Rs, EIG_ERR_ARG, "eig_lu_export: null argument");
     ensure_host(*lu);
-    std::copy(lu->Lp.begin(), lu->Lp.end(), Lp);
-    std::copy(lu->Lj.begin(), lu->Lj.end(), Lj);
-    std::copy(lu->Lx.begin(), lu->Lx.end(), Lx);
-    std::copy(lu->Up.begin(), lu->Up.end(), Up);
-    std::copy(lu->Ui.begin(), lu->Ui.end(), Ui);
-    std::copy(lu->Ux.begin(), lu->Ux.end(), Ux);
+    std::copy(lu->ex.Lp.begin(), lu->ex.Lp.end(), Lp);
+    std::copy(lu->ex.Lj.begin(), lu->ex.Lj.end(), Lj);
+    std::copy(lu->ex.Lx.begin(), lu->ex.Lx.end(), Lx);
+    std::copy(lu->ex.Up.begin(), lu->ex.Up.end(), Up);
+    std::copy(lu->ex.Ui.begin(), lu->ex.Ui.end(), Ui);
+    std::copy(lu->ex.Ux.begin(), lu->ex.Ux.end(), Ux);
     std::copy(lu->P.begin(), lu->P.end(), P);
     std::copy(lu->Q.begin(), lu->Q.end(), Q);
     std::copy(lu->Rs.begin(), lu->Rs.end(), Rs);
