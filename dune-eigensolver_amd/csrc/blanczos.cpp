@@ -148,29 +148,29 @@ double *dptr(DevBuf *b) { return b->d(); }
 
 // R0 diagonal spread beyond which CholQR2's second pass recomputes M Z instead of reusing (M Z) R0^-1
 constexpr double kCholQrReuseCond = 1e4;
+}  // namespace
 
-// Z (b columns) = Vdst R with Vdst M-orthonormal (CholQR twice); R (b x b upper, row-major) on
-// the host.  Vdst may equal Z.  The b x b factorisations run on the device (k_chol_small: the host
-// chol_upper / tri_upper_inv arithmetic).  One host round trip in the middle reads R0 back to pick
-// the second pass (reuse M Z or recompute it, below), one at the end brings R and the breakdown
-// flag back.  The pick is a heuristic: the spread of R0's diagonal is only a lower bound on
-// cond(R0), so an ill-conditioned block with an even diagonal can still take the reuse path (its
-// second pass then restores M-orthonormality to ~eps cond(Z) instead of ~eps).
-void mcholqr2(eig_blanczos_s &w, double *Z, double *Vdst, std::vector<double> &Rtot)
+namespace eigmi {
+// CholQR2 in the M-inner product (internal.h CholQr2), shared by block Lanczos and LOBPCG.
+bool mcholqr2_mv(const CholQr2 &q, double *Z, double *Vdst, std::vector<double> &Rtot, long long &recomputed)
 {
-  eig_mat_s &M = *w.M;
-  eig_ctx_t ctx = M.ctx;
+  eig_ctx_t ctx = q.ctx;
   hipStream_t s = ctx->stream;
-  const int b = w.b;
-  const i64 n = w.n, ld = w.ld, own = w.own;
-  double *Gd = w.small->d();
+  const int b = q.b;
+  const i64 n = q.n, ld = q.ld, own = q.own;
+  // M = I: M Z is Z itself, nothing to form or to carry
+  double *MZ = q.M ? q.MZ : Z;
+  double *Gd = q.small;
   double *Sd = Gd + (size_t)b * b;
-  double *Rd = w.chol->d(), *Rt = Rd + (size_t)b * b;
+  double *Rd = q.chol, *Rt = Rd + (size_t)b * b;
   int *flag = reinterpret_cast<int *>(Rt + (size_t)b * b);
   EIG_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
-  halo_mv(M, Z, b, s);
-  launch_spmm_mv8(M, b, Z, dptr(w.MZ), s);
-  launch_panel_gram(ctx, n, ld, b, b, Z + own * 8, dptr(w.MZ) + own * 8, Gd, s);
+  if (q.M)
+  {
+    halo_mv(*q.M, Z, b, s);
+    launch_spmm_mv8(*q.M, b, Z, MZ, s);
+  }
+  launch_panel_gram(ctx, n, ld, b, b, Z + own * 8, MZ + own * 8, Gd, s);
   allreduce_sum(ctx, Gd, (i64)b * b, s);
   launch_chol_small(b, 0, Gd, Rd, Sd, Rt, flag, s);  // Sd = R0^-1, Rt = R0
   // The second pass may reuse M Z updated by the same factor (row-local: M (Z R0^-1) = (M Z) R0^-1 up
@@ -189,34 +189,64 @@ void mcholqr2(eig_blanczos_s &w, double *Z, double *Vdst, std::vector<double> &R
     dmin = std::min(dmin, d);
   }
   const bool reuse = dmin > 0.0 && dmax <= kCholQrReuseCond * dmin;
-  w.cholqr_recomputed += !reuse;
-  if (reuse && b == 32)
+  recomputed += !reuse && q.M;
+  if (reuse && b == 32 && q.M && !q.finish_mz)
   {
     // Z <- Z R0^-1 and the second pass's Gram (Z R0^-1)^T (M Z R0^-1) in one pass over Z and M Z
     // (k_cholqr_fold): M Z R0^-1 is never stored, Z R0^-1 is not read back
-    launch_cholqr_fold(ctx, n, ld, Z + own * 8, dptr(w.MZ) + own * 8, Sd, Gd, s);
+    launch_cholqr_fold(ctx, n, ld, Z + own * 8, MZ + own * 8, Sd, Gd, s);
   }
   else
   {
     launch_panel_update(n, ld, ld, b, b, Z + own * 8, Sd, 1.0, 0.0, Z + own * 8, s);
-    if (reuse)
-      launch_panel_update(n, ld, ld, b, b, dptr(w.MZ) + own * 8, Sd, 1.0, 0.0, dptr(w.MZ) + own * 8, s);
-    else
+    if (q.M)
     {
-      halo_mv(M, Z, b, s);
-      launch_spmm_mv8(M, b, Z, dptr(w.MZ), s);
+      if (reuse)
+        launch_panel_update(n, ld, ld, b, b, MZ + own * 8, Sd, 1.0, 0.0, MZ + own * 8, s);
+      else
+      {
+        halo_mv(*q.M, Z, b, s);
+        launch_spmm_mv8(*q.M, b, Z, MZ, s);
+      }
     }
-    launch_panel_gram(ctx, n, ld, b, b, Z + own * 8, dptr(w.MZ) + own * 8, Gd, s);
+    launch_panel_gram(ctx, n, ld, b, b, Z + own * 8, MZ + own * 8, Gd, s);
   }
   allreduce_sum(ctx, Gd, (i64)b * b, s);
   launch_chol_small(b, 1, Gd, Rd, Sd, Rt, flag, s);  // Sd = R1^-1, Rt <- R1 R0
   launch_panel_update(n, ld, ld, b, b, Z + own * 8, Sd, 1.0, 0.0, Vdst + own * 8, s);
+  // the caller carries M Vdst: the same factor on M Z (row-local, as above)
+  if (q.finish_mz && q.M) launch_panel_update(n, ld, ld, b, b, MZ + own * 8, Sd, 1.0, 0.0, MZ + own * 8, s);
   Rtot.assign((size_t)b * b, 0.0);
   int hflag = 0;
   EIG_HIP(hipMemcpyAsync(Rtot.data(), Rt, Rtot.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   EIG_HIP(hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, s));
   EIG_HIP(hipStreamSynchronize(s));
-  EIG_CHECK(!hflag, EIG_ERR_BREAKDOWN,
+  return !hflag;
+}
+}  // namespace eigmi
+
+namespace {
+
+// Z (b columns) = Vdst R with Vdst M-orthonormal (CholQR twice); R (b x b upper, row-major) on
+// the host.  Vdst may equal Z.  The b x b factorisations run on the device (k_chol_small: the host
+// chol_upper / tri_upper_inv arithmetic).  One host round trip in the middle reads R0 back to pick
+// the second pass (reuse M Z or recompute it, below), one at the end brings R and the breakdown
+// flag back.  The pick is a heuristic: the spread of R0's diagonal is only a lower bound on
+// cond(R0), so an ill-conditioned block with an even diagonal can still take the reuse path (its
+// second pass then restores M-orthonormality to ~eps cond(Z) instead of ~eps).
+void mcholqr2(eig_blanczos_s &w, double *Z, double *Vdst, std::vector<double> &Rtot)
+{
+  CholQr2 q;
+  q.M = w.M;
+  q.ctx = w.M->ctx;
+  q.b = w.b;
+  q.n = w.n;
+  q.ld = w.ld;
+  q.own = w.own;
+  q.MZ = dptr(w.MZ);
+  q.small = w.small->d();
+  q.chol = w.chol->d();
+  EIG_CHECK(mcholqr2_mv(q, Z, Vdst, Rtot, w.cholqr_recomputed), EIG_ERR_BREAKDOWN,
             "block Lanczos: M-Gram of the new block is not positive definite (Krylov space exhausted)");
 }
 

@@ -562,6 +562,31 @@ void launch_panel_gram_2stage(eig_ctx_t ctx, i64 n, i64 ld, i64 m1, i64 m2, cons
 // of diag(M)^-1 M, from X = 0; blanczos.cpp): returns the buffer (Xa, Xb or Xc) holding x_degree.
 double *cheb_solve(eig_mat_s &M, i64 m, int degree, double lmin, double lmax, const double *Bv, const double *dinv,
                    double *Xa, double *Xb, double *Xc, hipStream_t s);
+// CholQR2 in the M-inner product (blanczos.cpp; block Lanczos and LOBPCG): Z (b columns) = Vdst R with
+// Vdst M-orthonormal, R (b x b upper, row-major) to the host in Rtot.  Vdst may equal Z.  M == nullptr is
+// M = I (MZ unused).  finish_mz: MZ = M Vdst on return (the factors applied to M Z as to Z; the fused
+// b = 32 middle step, which never stores M Z R0^-1, is then not taken).  `recomputed` counts second
+// passes that recomputed M Z.  False on a non-positive pivot (Vdst is then not usable).
+struct CholQr2 {
+  eig_mat_s *M = nullptr;
+  eig_ctx_t ctx = nullptr;
+  int b = 0;
+  i64 n = 0, ld = 0, own = 0;
+  double *MZ = nullptr;     // b columns, window layout
+  double *small = nullptr;  // 2 b b doubles: Gram, inverse factor
+  double *chol = nullptr;   // 2 b b doubles + 64 bytes: R, Rtot and the flag
+  bool finish_mz = false;
+};
+bool mcholqr2_mv(const CholQr2 &q, double *Z, double *Vdst, std::vector<double> &Rtot, long long &recomputed);
+// LOBPCG's streaming kernels (k_lobpcg.hip).  R = KX - MX diag(theta) (m columns, leading dimension
+// ld, pointers at owned row 0) and sums[j] = ||r_j||^2, sums[m + j] = ||(MX)_j||^2 (device; tickets
+// 0 .. m / 8 - 1 and the partials of ctx->red).
+void launch_lobpcg_resid(eig_ctx_t ctx, i64 n, i64 ld, i64 m, const double *KX, const double *MX,
+                         const double *theta, double *R, double *sums, hipStream_t s);
+// In place on S = [X | W | P] (m columns each; kb = 2: P is not read): X <- S C_x, P <- S C_p with
+// C = [C_x C_p] (kb m x 2 m, row-major, device); the same on KS and MS where given (one launch).
+void launch_lobpcg_update(eig_ctx_t ctx, i64 n, i64 ld, i64 m, int kb, double *S, double *KS, double *MS,
+                          const double *C, hipStream_t s);
 // Geometric multigrid inner solve (mg.cpp): X = S_cycles B on the level-0 matrix's window layout.
 void mg_apply(eig_mg_s &mg, i64 m, const double *B, double *X, int cycles);
 eig_mat_s *mg_matrix(const eig_mg_s &mg);

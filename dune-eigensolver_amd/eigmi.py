@@ -83,6 +83,12 @@ class BlockTiming(ctypes.Structure):
                [("steps", ctypes.c_int64), ("cheb_launches", ctypes.c_int64), ("cholqr_recomputed", ctypes.c_int64)]
 
 
+class LobpcgTiming(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("total_ms", "resid_ms", "precond_ms", "orth_ms", "spmm_ms", "rr_ms")] + \
+               [("iters", ctypes.c_int64), ("cholqr_recomputed", ctypes.c_int64), ("p_dropped", ctypes.c_int64),
+                ("orth_rejected", ctypes.c_int64), ("orth_dev", ctypes.c_double)]
+
+
 class Timing(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("spmv_ms", ctypes.c_double), ("update_ms", ctypes.c_double),
                 ("comm_ms", ctypes.c_double), ("spmv_launches", ctypes.c_int64)]
@@ -208,6 +214,15 @@ SIGNATURES = {
     "eig_mass_solve_mv8": (_int, [_vp, _i64, _int, _dbl, _dbl, _vp, _vp]),
     "eig_panel_update_mv8": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dbl, _dbl, _vp]),
     "eig_panel_gram_mv8": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "eig_lobpcg_create": (_int, [_vp, _vp, _int, _int, _vp, _u, ctypes.POINTER(_vp)]),
+    "eig_lobpcg_precond_cheb": (_int, [_vp, _vp, _int, _dbl, _dbl]),
+    "eig_lobpcg_precond_mg": (_int, [_vp, _vp, _int]),
+    "eig_lobpcg_step": (_int, [_vp, _int, _int, _dbl, ctypes.POINTER(_int), ctypes.POINTER(_int),
+                               ctypes.POINTER(LobpcgTiming)]),
+    "eig_lobpcg_ritz": (_int, [_vp, _int, _vp, _vp, _vp]),
+    "eig_lobpcg_destroy": (_int, [_vp]),
+    "eig_lobpcg_resid_mv8": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "eig_lobpcg_update_mv8": (_int, [_vp, _i64, _i64, _int, _vp, _vp]),
     "eig_flops_orthonormalize": (_dbl, [_i64, _i64]),
     "eig_bytes_orthonormalize_blocked": (_dbl, [_i64, _i64, _int]),
     "eig_gen_nnzb": (_i64, [_int, _int]),
@@ -800,6 +815,17 @@ def panel_gram_mv8(ctx, n, m1, m2, Q1, Q2, G):
     ctx.check(lib.eig_panel_gram_mv8(ctx.h, n, m1, m2, Q1.ptr, Q2.ptr, G.ptr))
 
 
+def lobpcg_resid_mv8(ctx, n, m, KX, MX, theta, R, sums):
+    """R = KX - MX diag(theta); sums[j] = ||r_j||^2, sums[m + j] = ||(MX)_j||^2 (eig_lobpcg_resid_mv8)."""
+    ctx.check(lib.eig_lobpcg_resid_mv8(ctx.h, n, m, KX.ptr, MX.ptr, theta.ptr, R.ptr, sums.ptr))
+
+
+def lobpcg_update_mv8(ctx, n, m, kb, S, C):
+    """In place on S = [X | W | P] (n x 3 m): X <- S C_x, P <- S C_p, C = [C_x C_p] (kb m x 2 m row-major)
+    (eig_lobpcg_update_mv8)."""
+    ctx.check(lib.eig_lobpcg_update_mv8(ctx.h, n, m, kb, S.ptr, C.ptr))
+
+
 def mass_solve_mv8(M, m, degree, B, X, lmin=0.5, lmax=2.5):
     """X = M^-1 B by `degree` Chebyshev-Jacobi steps (eig_mass_solve_mv8).  M: 1x1 blocks, or square
     blocks 2..4 on one rank -- then B and X have M.info.n = nb_rows * b scalar rows and [lmin, lmax]
@@ -1036,6 +1062,62 @@ class BlockLanczos:
     def close(self):
         if self.h and self.K.h and self.K.ctx.h:
             lib.eig_blanczos_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Lobpcg:
+    """eig_lobpcg_t: LOBPCG for K x = lambda M x (M = None: K x = lambda x), see include/eigmi.h.
+    K (and M): 1x1 blocks, or the same square blocks b = 2..4 (vectors have K.info.n = nb_rows * b scalar
+    rows).  X0: a DeviceArray holding the n x block start block (MultiVector<double,8> layout), or None for
+    the seeded random block.  Preconditioner: cheb=(degree, lmin, lmax[, Ap]) or mg=(Multigrid, cycles)."""
+
+    def __init__(self, K, M=None, block=8, which=WHICH_SA, X0=None, seed=123, cheb=None, mg=None):
+        self.K, self.M, self.block = K, M, block
+        self.mg = mg[0] if mg is not None else None
+        self.h = None
+        h = _vp()
+        K.ctx.check(lib.eig_lobpcg_create(K.h, M.h if M is not None else None, block, which,
+                                          X0.ptr if X0 is not None else None, seed, ctypes.byref(h)))
+        self.h = h
+        _track(self)
+        if cheb is not None:
+            self.precond_cheb(*cheb)
+        if mg is not None:
+            self.precond_mg(*mg)
+
+    def precond_cheb(self, degree, lmin, lmax, Ap=None):
+        self.Ap = Ap
+        self.K.ctx.check(lib.eig_lobpcg_precond_cheb(self.h, Ap.h if Ap is not None else None, degree, lmin, lmax))
+
+    def precond_mg(self, mg, cycles=1):
+        self.mg = mg
+        self.K.ctx.check(lib.eig_lobpcg_precond_mg(self.h, mg.h, cycles))
+
+    def step(self, max_iters, nev, tol):
+        """-> (iterations done, converged, LobpcgTiming); tol = 0 forces max_iters iterations."""
+        it, conv, t = _int(0), _int(0), LobpcgTiming()
+        self.K.ctx.check(lib.eig_lobpcg_step(self.h, max_iters, nev, tol, ctypes.byref(it), ctypes.byref(conv),
+                                             ctypes.byref(t)))
+        return it.value, bool(conv.value), t
+
+    def ritz(self, nev, want_evec=False, want_resid=True):
+        ev = np.zeros(nev)
+        n = self.K.info.n
+        evec = np.zeros(nev * n) if want_evec else None
+        res = np.zeros(nev) if want_resid else None
+        self.K.ctx.check(lib.eig_lobpcg_ritz(self.h, nev, _np_ptr(ev), _np_ptr(evec) if want_evec else None,
+                                             _np_ptr(res) if want_resid else None))
+        return ev, (evec.reshape(nev, n) if want_evec else None), res
+
+    def close(self):
+        if self.h and self.K.h and self.K.ctx.h:
+            lib.eig_lobpcg_destroy(self.h)
         self.h = None
 
     def __del__(self):

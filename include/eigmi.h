@@ -725,6 +725,70 @@ int eig_panel_update_mv8(eig_ctx_t ctx, int64_t n, int64_t m1, int64_t m2, const
                          double alpha, double beta, double *Y);
 int eig_panel_gram_mv8(eig_ctx_t ctx, int64_t n, int64_t m1, int64_t m2, const double *Q1, const double *Q2, double *G);
 
+/* ---------------------------------------------------------------- LOBPCG */
+/* K x = lambda M x (M = NULL: the standard problem) by LOBPCG: a block X of m = `block` vectors, the
+ * preconditioned residuals W = T (K X - M X diag(theta)) and the previous directions P, a Rayleigh-Ritz
+ * on span [X W P] per iteration.  The preconditioner only gives a search direction, so the iterates
+ * converge to the pencil's own eigenpairs whatever its accuracy (one multigrid V-cycle suffices), the
+ * memory does not grow with the iteration count (nine n x m panels, six when M = NULL, plus one for a
+ * preconditioner's input, two more for the Chebyshev recurrence, and the multigrid's own workspace), and
+ * a run can start from a given block.
+ * The basis is kept M-orthonormal (two Gram-Schmidt passes in the M-inner product and CholQR2 for W, as
+ * the block Lanczos), KX and MX are carried by the update, and every iteration checks max |S^T M S - I|
+ * <= 1e-10 with one more panel Gram before its Rayleigh-Ritz.  Convergence: ||K x_j - theta_j M x_j|| <=
+ * tol |theta_j| ||M x_j|| for j < nev, tested at the start of every iteration.
+ * (Without that check a W that lies numerically inside span [X P] -- residuals at the rounding floor --
+ * passes CholQR2 and hands the Rayleigh-Ritz null vectors as Ritz vectors of value 0)
+ * K (and M): 1x1 blocks, or the same square blocks b = 2..4 (vectors then have n = nb_rows * b scalar
+ * rows); rectangular or differing blocks: EIG_ERR_BLOCKSIZE.  One rank (a distributed context:
+ * EIG_ERR_ARG).  4 * block > n: EIG_ERR_SHAPE.  which: EIG_WHICH_SA or EIG_WHICH_LA.
+ * X0 (or NULL): the start block, n x block on the device (MultiVector<double,8> layout), any basis of its
+ * span; NULL: mt19937(seed) normals in MultiVector fill order, as eig_random_mv8. */
+typedef struct eig_lobpcg_s *eig_lobpcg_t;
+typedef struct eig_lobpcg_timing {
+  double total_ms;    /* device time of the iterations (events), the sum of the five below */
+  double resid_ms;    /* the residual and its column sums (k_lobpcg_resid) + the host's test */
+  double precond_ms;  /* W = T R */
+  double orth_ms;     /* two Gram-Schmidt passes against [X P] and the CholQR2 of W */
+  double spmm_ms;     /* K W */
+  double rr_ms;       /* H = S^T K S, the host eigenproblem and the update (k_lobpcg_update) */
+  int64_t iters;
+  int64_t cholqr_recomputed; /* CholQR2 second passes (since creation) that recomputed M W */
+  int64_t p_dropped;         /* iterations (since creation) redone without P after a non-positive pivot or a
+                                failed orthonormality check */
+  int64_t orth_rejected;     /* iterations (since creation, redone ones included) whose S = [X W P] missed
+                                max |S^T M S - I| <= 1e-10 after the CholQR2 of W */
+  double orth_dev;           /* largest max |S^T M S - I| an accepted iteration had (since creation) */
+} eig_lobpcg_timing;
+int eig_lobpcg_create(eig_mat_t K, eig_mat_t M, int block, int which, const double *X0, unsigned seed,
+                      eig_lobpcg_t *ws);
+/* T = `degree` Chebyshev-Jacobi steps on the SPD matrix Ap (NULL: K; blocks as K's, point Jacobi on blocks
+ * as in eig_mass_solve_mv8) with the spectrum of diag(Ap)^-1 Ap in [lmin, lmax].  T = `cycles` multigrid
+ * iterations (mg of K's context and size, max_cols >= block, else EIG_ERR_ARG; 1x1 blocks).  Without
+ * either call T = I.  A preconditioner with EIG_WHICH_LA: EIG_ERR_ARG. */
+int eig_lobpcg_precond_cheb(eig_lobpcg_t ws, eig_mat_t Ap, int degree, double lmin, double lmax);
+int eig_lobpcg_precond_mg(eig_lobpcg_t ws, eig_mg_t mg, int cycles);
+/* Up to max_iters iterations, stopping when the first nev pairs have converged (tol = 0: exactly
+ * max_iters iterations).  iters_done, converged, timing: outputs, or NULL.  A non-positive pivot in the
+ * CholQR2 of W, or a failed orthonormality check after it, redoes the iteration without P; without P it
+ * returns EIG_ERR_BREAKDOWN (X, theta as before that iteration; the workspace can still be destroyed). */
+int eig_lobpcg_step(eig_lobpcg_t ws, int max_iters, int nev, double tol, int *iters_done, int *converged,
+                    eig_lobpcg_timing *timing);
+/* The first nev <= block Ritz pairs: eval_host[nev] (SA ascending / LA descending), evec_host: nev vectors
+ * of n rows with y^T M y = 1 (or NULL), resid_host[nev]: ||K y - theta M y||_2 from fresh products (or
+ * NULL).  With resid_host it overwrites the workspace's W slices and residual buffer, which are scratch
+ * between eig_lobpcg_step calls. */
+int eig_lobpcg_ritz(eig_lobpcg_t ws, int nev, double *eval_host, double *evec_host, double *resid_host);
+int eig_lobpcg_destroy(eig_lobpcg_t ws);
+/* LOBPCG's streaming kernels on n-row MultiVector<double,8> buffers (m in {8,16,24,32}):
+ * R = KX - MX diag(theta) with r = kx - theta * mx one product and one subtraction, and sums_dev[j] =
+ * ||r_j||^2, sums_dev[m + j] = ||(MX)_j||^2 (deterministic reductions: run-to-run bitwise equal);
+ * S = [X | W | P] (n x 3 m; kb = 2: the P slice is written, not read) updated in place to X' = S C_x,
+ * P' = S C_p with C = [C_x C_p] (kb m x 2 m, row-major, device) on MFMA; W stays. */
+int eig_lobpcg_resid_mv8(eig_ctx_t ctx, int64_t n, int64_t m, const double *KX, const double *MX,
+                         const double *theta_dev, double *R, double *sums_dev);
+int eig_lobpcg_update_mv8(eig_ctx_t ctx, int64_t n, int64_t m, int kb, double *S, const double *C_dev);
+
 /* a14: the reference's analytic GS models (kernels_cpp.hh:98-116, :157-175). */
 double eig_flops_orthonormalize(int64_t n, int64_t m);
 double eig_bytes_orthonormalize_blocked(int64_t n, int64_t m, int b);

@@ -157,6 +157,15 @@ class Matrix {
     check(eig_mat_create_bcsr(ctx.get(), nrows, ncols, br, bc, rowptr.data(), col.data(), val.data(), &m), ctx.get());
     return Matrix(ctx.get(), m);
   }
+  // Block CSR arrays as eig_mat_create_bcsr takes them (square: nrows block rows and columns)
+  static Matrix from_bcsr(const Context &ctx, const std::vector<int64_t> &rowptr, const std::vector<int32_t> &col,
+                          const std::vector<double> &val, int br = 1, int bc = 1)
+  {
+    const int64_t nrows = (int64_t)rowptr.size() - 1;
+    eig_mat_t m = nullptr;
+    check(eig_mat_create_bcsr(ctx.get(), nrows, nrows, br, bc, rowptr.data(), col.data(), val.data(), &m), ctx.get());
+    return Matrix(ctx.get(), m);
+  }
   Matrix(Matrix &&o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
   Matrix(const Matrix &) = delete;
   Matrix &operator=(const Matrix &) = delete;
@@ -602,6 +611,52 @@ void computeGenNonSymShiftInvertMinMagnitude(const Matrix &A, const Matrix &B, d
 {
   detail::nonsym(A, B, epsilon, x, lambda, sigma, EIG_ARNOLDI_GEN, maxit);
 }
+
+// ------------------------------------------------------------------------------------ LOBPCG
+// K x = lambda M x (M = nullptr: K x = lambda x) by LOBPCG (eig_lobpcg_*, include/eigmi.h): the smallest
+// end with an optional Chebyshev-Jacobi preconditioner, or the largest end without one.  The matrices
+// must outlive the solver.
+class Lobpcg {
+ public:
+  Lobpcg(const Matrix &K, const Matrix *M, int block, int which = EIG_WHICH_SA, unsigned seed = 123,
+         const double *X0_device = nullptr)
+      : ctx_(K.ctx()), n_((std::size_t)K.info().n)
+  {
+    check(eig_lobpcg_create(K.get(), M ? M->get() : nullptr, block, which, X0_device, seed, &h_), ctx_);
+  }
+  Lobpcg(const Lobpcg &) = delete;
+  Lobpcg &operator=(const Lobpcg &) = delete;
+  ~Lobpcg() { eig_lobpcg_destroy(h_); }
+  // `degree` Chebyshev-Jacobi steps on Ap (nullptr: K) with the spectrum of diag(Ap)^-1 Ap in [lmin, lmax]
+  void precond_cheb(int degree, double lmin, double lmax, const Matrix *Ap = nullptr)
+  {
+    check(eig_lobpcg_precond_cheb(h_, Ap ? Ap->get() : nullptr, degree, lmin, lmax), ctx_);
+  }
+  // up to max_iters iterations; true when the first nev pairs hold ||K x - theta M x|| <= tol theta ||M x||
+  bool step(int max_iters, int nev, double tol, int *iters_done = nullptr, eig_lobpcg_timing *timing = nullptr)
+  {
+    int conv = 0;
+    check(eig_lobpcg_step(h_, max_iters, nev, tol, iters_done, &conv, timing), ctx_);
+    return conv != 0;
+  }
+  // the first nev Ritz values, vectors (nev x n, row per vector; may be null) and true residuals (may be null)
+  void ritz(int nev, std::vector<double> &lambda, std::vector<double> *vectors = nullptr,
+            std::vector<double> *residuals = nullptr)
+  {
+    lambda.resize(nev);
+    if (vectors) vectors->resize((std::size_t)nev * n_);
+    if (residuals) residuals->resize(nev);
+    check(eig_lobpcg_ritz(h_, nev, lambda.data(), vectors ? vectors->data() : nullptr,
+                          residuals ? residuals->data() : nullptr),
+          ctx_);
+  }
+  eig_lobpcg_t get() const { return h_; }
+
+ private:
+  eig_ctx_t ctx_;
+  std::size_t n_;
+  eig_lobpcg_t h_ = nullptr;
+};
 
 }  // namespace eigmi
 

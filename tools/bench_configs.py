@@ -15,6 +15,8 @@
   C5  generalised K x = lambda M x, P1 on the Kuhn split (15-pt shared pattern), block Lanczos
       k = 32: block steps/s with the phase split, the fused Chebyshev SpMM kernel against
       12 nnz + 4 (n+1) + (32 m + 8) n bytes per m-column launch (EIGMI_C5_N, default 256)
+  LOBPCG  the smallest end of the C5 pencil by LOBPCG with one multigrid V-cycle per iteration, its two
+      streaming kernels alone, the fused update A/B against four panel updates, and c5si beside it
 
 One JSON line per measurement; algorithmic bytes per SURVEY 8(d); peak 8 TB/s.
 """
@@ -616,6 +618,114 @@ def c5si(ctx):
               f"lowest eigenvalue of -Laplace on the unit cube is 3 pi^2 = {3 * np.pi ** 2:.4f} (h = {h:.5f})")
     bl.close()
     mg.close()
+
+
+class _View:
+    """A slice of a device buffer, for the wrappers that take an object with .ptr."""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+
+def lobpcg(ctx):
+    """The smallest end of the C5 pencil by LOBPCG (eig_lobpcg_*): block 32, nev 8, one multigrid
+    V-cycle per iteration as the preconditioner, tol 1e-8, to convergence (at most EIGMI_LOBPCG_ITERS = 40
+    iterations, one per call with a record each) -- iterations, the per-iteration split of
+    eig_lobpcg_timing, the true residuals; then the two streaming kernels alone
+    (k_lobpcg_resid, k_lobpcg_update against their algorithmic bytes) with an interleaved A/B, five
+    rounds, of the fused update against the same update by four eig_panel_update_mv8 calls (two
+    products into scratch panels, two copies back through the identity -- the kernels the update
+    replaces); then c5si in the same process."""
+    N = int(os.environ.get("EIGMI_C5_N", "256"))
+    b, nev, tol = 32, 8, 1e-8
+    n = N ** 3
+    tag = f"C5 P1 Kuhn K/M {N}^3" + (" (variable coefficients, box image)" if c5_var() else "")
+    t0 = time.perf_counter()
+    K, M, _ = c5_mats(ctx, N)
+    mg = eigmi.Multigrid(K, (N, N, N), max_cols=b, smooth_degree=2, smooth_ratio=5.0)
+    s = eigmi.Lobpcg(K, M, block=b, seed=123, mg=(mg, 1))
+    setup_s = time.perf_counter() - t0
+    # one iteration per call, so that every iteration leaves a record: theta, the largest ||r_j|| / |theta_j|
+    # of the nev wanted pairs (true residuals from fresh products; the convergence bar is on
+    # ||r_j|| / (|theta_j| ||M x_j||), which is larger by 1 / ||M x_j||), and the counters since creation.
+    # Each call ends with the residual its convergence test needs, so resid_ms counts two per iteration.
+    it, conv, tw = 0, False, 0.0
+    acc = dict(total_ms=0.0, resid_ms=0.0, precond_ms=0.0, orth_ms=0.0, spmm_ms=0.0, rr_ms=0.0)
+    t = None
+    for _ in range(int(os.environ.get("EIGMI_LOBPCG_ITERS", "40"))):
+        try:
+            dt, (done, conv, t) = wall(lambda: s.step(1, nev, tol))
+        except eigmi.EigError as err:  # EIG_ERR_BREAKDOWN: recorded, the kernel measurements below still run
+            emit(config=tag, op="LOBPCG iteration", iteration=it + 1, error=str(err))
+            break
+        tw += dt
+        it += done
+        for k in acc:
+            acc[k] += getattr(t, k)
+        ev, _, res = s.ritz(nev)
+        emit(config=tag, op="LOBPCG iteration", iteration=it, converged=conv, theta=[float(x) for x in ev[:3]],
+             theta_nev=float(ev[-1]), resid_over_theta=float((res / np.abs(ev)).max()),
+             cholqr_recomputed=int(t.cholqr_recomputed), p_dropped=int(t.p_dropped),
+             orth_rejected=int(t.orth_rejected), orth_dev=float(t.orth_dev))
+        if conv or done == 0:
+            break
+    ev, _, res = s.ritz(nev)
+    per = lambda x: round(x / max(it, 1), 2)  # noqa: E731
+    emit(config=tag + f", LOBPCG block {b}, nev {nev}, one V-cycle, tol {tol:g}", op="solve to convergence",
+         iterations=it, converged=conv, total_ms=round(acc["total_ms"], 1), wall_s=round(tw, 3),
+         ms_per_iteration=per(acc["total_ms"]), resid_ms=per(acc["resid_ms"]), precond_ms=per(acc["precond_ms"]),
+         orth_ms=per(acc["orth_ms"]), spmm_ms=per(acc["spmm_ms"]), rr_update_ms=per(acc["rr_ms"]),
+         cholqr_recomputed=int(t.cholqr_recomputed), p_dropped=int(t.p_dropped), orth_rejected=int(t.orth_rejected),
+         orth_dev=float(t.orth_dev), eigenvalues=[float(x) for x in ev], true_residuals=[float(x) for x in res],
+         relative_residuals=[float(r / abs(e)) for r, e in zip(res, ev)], mg=mg.info(), setup_s=round(setup_s, 1))
+    s.close()
+    mg.close()
+    K.close(), M.close()
+    # the streaming kernels alone, one family: S = [X | W | P] random, C random orthonormal
+    rng = np.random.default_rng(5)
+    S = ctx.zeros(3 * n * b)
+    ctx.check(eigmi.lib.eig_fill_normal(ctx.h, 3 * n * b, 7, S.ptr))
+    C = np.linalg.qr(rng.standard_normal((3 * b, 2 * b)))[0]
+    dC = ctx.array(C)
+    dCx, dCp, dI = ctx.array(np.ascontiguousarray(C[:, :b])), ctx.array(np.ascontiguousarray(C[:, b:])), ctx.array(np.eye(b))
+    T1, T2 = ctx.zeros(n * b), ctx.zeros(n * b)
+    Xs, Ps = _View(S.offset(0)), _View(S.offset(2 * n * b))  # the X and P slices of S
+
+    def fused():
+        eigmi.lobpcg_update_mv8(ctx, n, b, 3, S, dC)
+        ctx.sync()
+
+    def four_calls():
+        eigmi.panel_update_mv8(ctx, n, 3 * b, b, S, dCx, 1.0, 0.0, T1)
+        eigmi.panel_update_mv8(ctx, n, 3 * b, b, S, dCp, 1.0, 0.0, T2)
+        eigmi.panel_update_mv8(ctx, n, b, b, T1, dI, 1.0, 0.0, Xs)
+        eigmi.panel_update_mv8(ctx, n, b, b, T2, dI, 1.0, 0.0, Ps)
+        ctx.sync()
+
+    fused(), four_calls()  # warm-up
+    rounds = {"fused": [], "four_calls": []}
+    for _ in range(5):
+        rounds["fused"].append(wall(fused, 3)[0] * 1e3)
+        rounds["four_calls"].append(wall(four_calls, 3)[0] * 1e3)
+    upd_bytes = (3 * b + 2 * b) * 8 * n
+    fm = float(np.median(rounds["fused"]))
+    emit(config=tag, op=f"k_lobpcg_update m={b} kb=3, one family, against four eig_panel_update_mv8 calls (interleaved, 5 rounds)",
+         fused_ms=[round(x, 3) for x in rounds["fused"]], four_calls_ms=[round(x, 3) for x in rounds["four_calls"]],
+         fused_median_ms=round(fm, 3), four_calls_median_ms=round(float(np.median(rounds["four_calls"])), 3),
+         bytes=upd_bytes, fused_GBs=round(upd_bytes / fm / 1e6, 1), frac=round(upd_bytes / fm / 1e6 / PEAK, 4))
+    th, sums = ctx.array(rng.standard_normal(b)), ctx.zeros(2 * b)
+
+    def resid():
+        eigmi.lobpcg_resid_mv8(ctx, n, b, Xs, Ps, th, T1, sums)
+        ctx.sync()
+
+    resid()
+    tr = wall(resid, 5)[0] * 1e3
+    emit(config=tag, op=f"k_lobpcg_resid m={b}", ms=round(tr, 3), bytes=3 * b * 8 * n,
+         GBs=round(3 * b * 8 * n / tr / 1e6, 1), frac=round(3 * b * 8 * n / tr / 1e6 / PEAK, 4))
+    for d in (S, T1, T2, dC, dCx, dCp, dI, th, sums):
+        d.free()
+    c5si(ctx)
 
 
 if __name__ == "__main__":

@@ -19,6 +19,8 @@
 #   boxk                 row-class box kernels alone (SpMM, Chebyshev step) at 256^3 under a kernel trace -> boxk.jsonl, boxk_trace/
 #   c5 | c5si            block Lanczos 256^3: largest end / smallest end (multigrid solve)  -> c5*.jsonl
 #   c5trace              both under a kernel trace                            -> c5_trace/, c5si_trace/
+#   lobpcg | lobpcgtrace LOBPCG on the variable-coefficient C5 pencil 256^3 (one V-cycle), its kernels' A/B and
+#                        c5si in one process; the same under a kernel trace   -> lobpcg.jsonl, lobpcg_trace/
 #   latency              fused step vs eig_mv across sizes and slabs, plane-run counts  -> latency.jsonl
 #   marchcopy            the march streams alone (tools/march_copy.hip)       -> march_copy.jsonl
 #   prefetch             geometric march prefetch variants x plane runs (256^3, 128^3, slab) -> latency.jsonl
@@ -121,6 +123,13 @@ run_task() {
       EIGMI_C5_N=256 timeout -k 10 300 python -u tools/bench_configs.py c5 > "$O/c5.jsonl" 2> "$O/c5.err" ;;
     c5si)
       EIGMI_C5_N=256 timeout -k 10 600 python -u tools/bench_configs.py c5si > "$O/c5si.jsonl" 2> "$O/c5si.err" ;;
+    lobpcg)
+      EIGMI_C5_N=256 EIGMI_C5_VAR=1 timeout -k 10 900 python -u tools/bench_configs.py lobpcg > "$O/lobpcg.jsonl" 2> "$O/lobpcg.err" ;;
+    lobpcgtrace)
+      # the same under a kernel trace: k_lobpcg_update / k_lobpcg_resid and the rest of an iteration per kernel
+      prof_env
+      EIGMI_C5_N=256 EIGMI_C5_VAR=1 timeout -k 10 1100 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/lobpcg_trace" -o trace -- \
+        python3 tools/bench_configs.py lobpcg > "$O/lobpcgt.jsonl" 2> "$O/lobpcgt.err" ;;
     c5trace)
       # C5 block steps (both ends) under a kernel trace: the per-kernel split of a block step
       prof_env
