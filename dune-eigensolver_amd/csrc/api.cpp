@@ -1611,6 +1611,21 @@ extern "C" int eig_spmm_blk_mv8(eig_mat_t A, int64_t m, const double *Qin, doubl
   });
 }
 
+extern "C" int eig_resid_mv8(eig_mat_t A, int64_t m, const double *X, const double *B, double *R)
+{
+  return guard(A ? A->ctx : nullptr, [&] {
+    EIG_CHECK(A && X && B && R, EIG_ERR_ARG, "eig_resid_mv8: null argument");
+    EIG_CHECK(R != X, EIG_ERR_ARG, "eig_resid_mv8: R must not alias X");
+    EIG_MV8_CHECK(m);
+    EIG_CHECK(A->br == A->bc && A->br >= 1 && A->br <= 4, EIG_ERR_BLOCKSIZE,
+              "eig_resid_mv8: square blocks 1..4 required");
+    EIG_CHECK(A->nb_rows == A->nb_cols && !A->ctx->distributed(), EIG_ERR_SHAPE,
+              "eig_resid_mv8: square single-rank matrix required");
+    DeviceGuard dg(A->ctx->device);
+    if (m > 0) launch_resid_mv8(*A, m, X, B, R, A->ctx->stream);
+  });
+}
+
 extern "C" int eig_dot_diag_mv8(eig_ctx_t ctx, int64_t n, int64_t m, const double *Q1, const double *Q2, double *dp)
 {
   return guard(ctx, [&] {

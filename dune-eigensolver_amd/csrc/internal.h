@@ -548,6 +548,16 @@ int cheb_step_launches(const eig_mat_s &M, i64 m);
 // launch_cheb_step dispatches here.  Vectors have nb_rows * br scalar rows, dinv is the scalar diagonal's.
 void launch_cheb_step_blk(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *B,
                           const double *dinv, double omega, double gamma, hipStream_t s);
+// The block-Jacobi instance of that step (the multigrid smoother on blocks): binv holds the inverse of the
+// diagonal block of every block row (br x br row-major, nb_rows of them), z = D_I^-1 (b - M x_k) in place of
+// the scalar scaling; and its first step X = gamma D^-1 B.  Same requirements as launch_cheb_step_blk.
+void launch_cheb_step_bjac(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *B,
+                           const double *binv, double omega, double gamma, hipStream_t s);
+void launch_cheb_init_bjac(const eig_mat_s &M, i64 m, const double *B, const double *binv, double gamma, double *X,
+                           hipStream_t s);
+// R = B - A X on square blocks 2..4 (k_mv8.hip k_spmm_blk_mv8_resid; one rank, R may alias B, never X):
+// launch_resid_mv8 dispatches here.
+void launch_resid_blk_mv8(const eig_mat_s &A, i64 m, const double *X, const double *B, double *R, hipStream_t s);
 // dinv[i] = 1 / a_ii over the owned scalar rows: 1x1 blocks, or (one rank) the scalar diagonal of the
 // diagonal blocks of square blocks 2..4
 void launch_diag_inv(const eig_mat_s &A, double *dinv, hipStream_t s);

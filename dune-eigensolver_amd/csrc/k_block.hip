@@ -438,6 +438,12 @@ void launch_sell_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, hipS
 void launch_resid_mv8(const eig_mat_s &A, i64 m, const double *X, const double *B, double *R, hipStream_t s)
 {
   // R = B - A X; R may be B (each row reads its own B entry before writing it), never X
+  if (A.br == A.bc && A.br > 1)
+  {
+    // square blocks 2..4: the residual epilogue on the blocked product (k_mv8.hip)
+    launch_resid_blk_mv8(A, m, X, B, R, s);
+    return;
+  }
   if (launch_box_resid(A, m, X, B, R, s)) return;
   sell_mv8<kResid>(A, m, X, R, B, nullptr, 0.0, 0.0, s);
 }

@@ -201,7 +201,13 @@ __global__ __launch_bounds__(256) void k_spmm_blk_mv8(i64 nbrows, i64 nslices, c
 // and x_{k-1} are read once (nontemporal loads, nontemporal stores of the result); the row's own x_k
 // was gathered through the diagonal block a moment ago.  Every epilogue access is under the store's
 // guards (row < nbrows, b0 + q < nblk_total).
-template <int B, int MB>
+//
+// BJ (block Jacobi, the multigrid smoother on blocks): dinv holds D_I^-1, the inverse of the diagonal block
+// of every block row (B x B row-major), and the scaling becomes z = D_I^-1 t with t = b - acc over the
+// node's B rows (z_r = sum over c = 0..B-1 in order of dinv[r][c] t_c, products and sums rounded
+// separately), x_{k+1} = omega (x_k + gamma z - x_{k-1}) + x_{k-1}.  The B^2 doubles are loaded here, after
+// the product's value registers are dead.  The point instance (BJ = false) is the code it was.
+template <int B, int MB, bool BJ = false>
 __global__ __launch_bounds__(256) void k_spmm_blk_mv8_cheb(i64 nbrows, i64 nslices, const i64 *__restrict__ slice_ptr,
                                                            const double *__restrict__ val,
                                                            const i32 *__restrict__ col, const double *__restrict__ Xk,
@@ -221,9 +227,17 @@ __global__ __launch_bounds__(256) void k_spmm_blk_mv8_cheb(i64 nbrows, i64 nslic
     const i64 row = s * 64 + ri;
     if (row < nbrows)
     {
-      double gd[B];
+      double gd[BJ ? B * B : B];
+      if constexpr (BJ)
+      {
 #pragma unroll
-      for (int r = 0; r < B; ++r) gd[r] = gamma * __builtin_nontemporal_load(dinv + row * B + r);
+        for (int t = 0; t < B * B; ++t) gd[t] = __builtin_nontemporal_load(dinv + row * (B * B) + t);
+      }
+      else
+      {
+#pragma unroll
+        for (int r = 0; r < B; ++r) gd[r] = gamma * __builtin_nontemporal_load(dinv + row * B + r);
+      }
 #pragma unroll
       for (int q = 0; q < MB; ++q)
         if (b0 + q < nblk_total)
@@ -237,6 +251,27 @@ __global__ __launch_bounds__(256) void k_spmm_blk_mv8_cheb(i64 nbrows, i64 nslic
             bb[r] = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(Bv + at + r * 8));
             xo[r] = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(Xold + at + r * 8));
           }
+          if constexpr (BJ)
+          {
+            dv2 t[B];
+#pragma unroll
+            for (int r = 0; r < B; ++r) t[r] = dv2{bb[r].x - acc[q][r].x, bb[r].y - acc[q][r].y};
+#pragma unroll
+            for (int r = 0; r < B; ++r)
+            {
+              dv2 z = dv2{0.0, 0.0};
+#pragma unroll
+              for (int c = 0; c < B; ++c)
+              {
+                z.x += gd[r * B + c] * t[c].x;
+                z.y += gd[r * B + c] * t[c].y;
+              }
+              const double o0 = omega * (xk[r].x + gamma * z.x - xo[r].x) + xo[r].x;
+              const double o1 = omega * (xk[r].y + gamma * z.y - xo[r].y) + xo[r].y;
+              __builtin_nontemporal_store(dv2{o0, o1}, reinterpret_cast<dv2 *>(Xold + at + r * 8));
+            }
+            continue;
+          }
 #pragma unroll
           for (int r = 0; r < B; ++r)
           {
@@ -245,6 +280,80 @@ __global__ __launch_bounds__(256) void k_spmm_blk_mv8_cheb(i64 nbrows, i64 nslic
             __builtin_nontemporal_store(dv2{o0, o1}, reinterpret_cast<dv2 *>(Xold + at + r * 8));
           }
         }
+    }
+  }
+}
+
+// R = Bv - A X: the residual epilogue on the blocked product (the multigrid's residual on blocks).  The same
+// image, lane mapping, slice walk and row sums as k_spmm_blk_mv8 (spmm_blk_row), then one subtraction per
+// element; every epilogue access is under the store's guards (row < nbrows, b0 + q < nblk_total).  R may be
+// Bv (each lane reads its own B entries before it stores them), never X (the gathered input).
+template <int B, int MB>
+__global__ __launch_bounds__(256) void k_spmm_blk_mv8_resid(i64 nbrows, i64 nslices, const i64 *__restrict__ slice_ptr,
+                                                            const double *__restrict__ val,
+                                                            const i32 *__restrict__ col, const double *__restrict__ X,
+                                                            double *R, i64 n, int nblk_total, int xcd_map,
+                                                            const double *Bv)
+{
+  const int wave = threadIdx.x >> 6, L = threadIdx.x & 63;
+  const int cp = L & 3;
+  const int ri = wave * 16 + (L >> 2);
+  const int b0 = blockIdx.y * MB;
+  const BlkSliceWalk w = blk_slice_walk(nslices, xcd_map);
+  for (i64 s = w.s0; s < w.s1; s += w.step)
+  {
+    double2 acc[MB][B];
+    spmm_blk_row<B, MB>(slice_ptr, val, col, X, n, nblk_total, b0, s, ri, cp, acc);
+    const i64 row = s * 64 + ri;
+    if (row < nbrows)
+    {
+#pragma unroll
+      for (int q = 0; q < MB; ++q)
+        if (b0 + q < nblk_total)
+        {
+          const i64 at = ((i64)(b0 + q) * n + row * B) * 8 + 2 * cp;
+          dv2 bb[B];
+#pragma unroll
+          for (int r = 0; r < B; ++r) bb[r] = *reinterpret_cast<const dv2 *>(Bv + at + r * 8);
+#pragma unroll
+          for (int r = 0; r < B; ++r)
+            *reinterpret_cast<dv2 *>(R + at + r * 8) = dv2{bb[r].x - acc[q][r].x, bb[r].y - acc[q][r].y};
+        }
+    }
+  }
+}
+
+// X = gamma D^-1 Bv with the block-diagonal D (binv: B x B row-major inverse per block row): the first step of
+// the block-Jacobi Chebyshev recurrence, k_cheb_init's counterpart.  One thread per (column block, node, 16-B
+// quarter); z_r summed over c = 0..B-1 in order as in k_spmm_blk_mv8_cheb<.., true>, then gamma * z_r.
+template <int B>
+__global__ __launch_bounds__(256) void k_cheb_init_bjac(i64 nbrows, int nblk, const double *__restrict__ Bv,
+                                                        const double *__restrict__ binv, double gamma,
+                                                        double *__restrict__ X)
+{
+  const i64 total = nbrows * nblk * 4;
+  for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256)
+  {
+    const int cp = (int)(idx & 3);
+    const i64 nr = idx >> 2, cb = nr / nbrows, row = nr - cb * nbrows;
+    const i64 at = (cb * nbrows * B + row * B) * 8 + 2 * cp;
+    double d[B * B];
+    dv2 t[B];
+#pragma unroll
+    for (int e = 0; e < B * B; ++e) d[e] = binv[row * (B * B) + e];
+#pragma unroll
+    for (int r = 0; r < B; ++r) t[r] = *reinterpret_cast<const dv2 *>(Bv + at + r * 8);
+#pragma unroll
+    for (int r = 0; r < B; ++r)
+    {
+      dv2 z = dv2{0.0, 0.0};
+#pragma unroll
+      for (int c = 0; c < B; ++c)
+      {
+        z.x += d[r * B + c] * t[c].x;
+        z.y += d[r * B + c] * t[c].y;
+      }
+      *reinterpret_cast<dv2 *>(X + at + r * 8) = dv2{gamma * z.x, gamma * z.y};
     }
   }
 }
@@ -281,7 +390,7 @@ static void launch_spmm_blk_mb(const eig_mat_s &A, int nblk, const double *Qin, 
 // The Chebyshev step on blocks: one launch for all column blocks (grid.y), the product's grid and
 // column blocks per workgroup (the epilogue's loads come after the product's value registers are dead:
 // DESIGN.md "Block Lanczos on blocks" has the register counts).
-template <int B>
+template <int B, bool BJ = false>
 static void launch_cheb_blk(const eig_mat_s &M, int nblk, const double *Xk, double *Xold, const double *Bv,
                             const double *dinv, double omega, double gamma, hipStream_t s)
 {
@@ -289,8 +398,73 @@ static void launch_cheb_blk(const eig_mat_s &M, int nblk, const double *Xk, doub
   const int gy = (nblk + MB - 1) / MB;
   bool xcd;
   const int gx = spmm_blk_grid_x(M, xcd);
-  hipLaunchKernelGGL((k_spmm_blk_mv8_cheb<B, MB>), dim3(gx, gy), dim3(256), 0, s, M.nb_rows, M.nslices, M.slice_ptr,
-                     M.val, M.col, Xk, Xold, M.nb_rows * B, nblk, xcd ? 1 : 0, Bv, dinv, omega, gamma);
+  hipLaunchKernelGGL((k_spmm_blk_mv8_cheb<B, MB, BJ>), dim3(gx, gy), dim3(256), 0, s, M.nb_rows, M.nslices,
+                     M.slice_ptr, M.val, M.col, Xk, Xold, M.nb_rows * B, nblk, xcd ? 1 : 0, Bv, dinv, omega, gamma);
+}
+
+template <int B>
+static void launch_resid_blk(const eig_mat_s &A, int nblk, const double *X, const double *Bv, double *R, hipStream_t s)
+{
+  constexpr int MB = spmm_blk_mb<B>();
+  const int gy = (nblk + MB - 1) / MB;
+  bool xcd;
+  const int gx = spmm_blk_grid_x(A, xcd);
+  hipLaunchKernelGGL((k_spmm_blk_mv8_resid<B, MB>), dim3(gx, gy), dim3(256), 0, s, A.nb_rows, A.nslices, A.slice_ptr,
+                     A.val, A.col, X, R, A.nb_rows * B, nblk, xcd ? 1 : 0, Bv);
+}
+
+static void check_blk_square(const eig_mat_s &M, const char *who)
+{
+  EIG_CHECK(M.br == M.bc && M.br >= 2 && M.br <= 4, EIG_ERR_BLOCKSIZE, std::string(who) + ": square blocks 2..4");
+  EIG_CHECK(!M.ctx->distributed(), EIG_ERR_ARG, std::string(who) + ": single rank only");
+  EIG_CHECK(M.R == 1 && M.nb_rows == M.nb_cols, EIG_ERR_SHAPE, std::string(who) + ": square matrix required");
+}
+
+void launch_resid_blk_mv8(const eig_mat_s &A, i64 m, const double *X, const double *Bv, double *R, hipStream_t s)
+{
+  const int nblk = (int)(m / 8);
+  check_blk_square(A, "blocked residual");
+  EIG_CHECK(X != R, EIG_ERR_ARG, "blocked residual: R must not be X");
+  if (nblk <= 0 || A.nb_rows <= 0) return;
+  switch (A.br)
+  {
+    case 2: launch_resid_blk<2>(A, nblk, X, Bv, R, s); break;
+    case 3: launch_resid_blk<3>(A, nblk, X, Bv, R, s); break;
+    default: launch_resid_blk<4>(A, nblk, X, Bv, R, s); break;
+  }
+  EIG_HIP(hipGetLastError());
+}
+
+void launch_cheb_step_bjac(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *Bv,
+                           const double *binv, double omega, double gamma, hipStream_t s)
+{
+  const int nblk = (int)(m / 8);
+  check_blk_square(M, "block-Jacobi Chebyshev step");
+  EIG_CHECK(Xk != Xold, EIG_ERR_ARG, "block-Jacobi Chebyshev step: x_k must not be the output buffer");
+  if (nblk <= 0 || M.nb_rows <= 0) return;
+  switch (M.br)
+  {
+    case 2: launch_cheb_blk<2, true>(M, nblk, Xk, Xold, Bv, binv, omega, gamma, s); break;
+    case 3: launch_cheb_blk<3, true>(M, nblk, Xk, Xold, Bv, binv, omega, gamma, s); break;
+    default: launch_cheb_blk<4, true>(M, nblk, Xk, Xold, Bv, binv, omega, gamma, s); break;
+  }
+  EIG_HIP(hipGetLastError());
+}
+
+void launch_cheb_init_bjac(const eig_mat_s &M, i64 m, const double *Bv, const double *binv, double gamma, double *X,
+                           hipStream_t s)
+{
+  const int nblk = (int)(m / 8);
+  check_blk_square(M, "block-Jacobi first step");
+  if (nblk <= 0 || M.nb_rows <= 0) return;
+  const int g = grid_for(M.nb_rows * nblk * 4, 256, kStreamBlocks);
+  switch (M.br)
+  {
+    case 2: hipLaunchKernelGGL(k_cheb_init_bjac<2>, dim3(g), dim3(256), 0, s, M.nb_rows, nblk, Bv, binv, gamma, X); break;
+    case 3: hipLaunchKernelGGL(k_cheb_init_bjac<3>, dim3(g), dim3(256), 0, s, M.nb_rows, nblk, Bv, binv, gamma, X); break;
+    default: hipLaunchKernelGGL(k_cheb_init_bjac<4>, dim3(g), dim3(256), 0, s, M.nb_rows, nblk, Bv, binv, gamma, X); break;
+  }
+  EIG_HIP(hipGetLastError());
 }
 
 void launch_cheb_step_blk(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *Bv,

@@ -166,6 +166,7 @@ SIGNATURES = {
     "eig_stream_copy_timed": (_int, [_vp, _i64, _vp, _vp, _int, _int, ctypes.POINTER(_dbl)]),
     "eig_spmm_mv8": (_int, [_vp, _i64, _vp, _vp]),
     "eig_spmm_blk_mv8": (_int, [_vp, _i64, _vp, _vp]),
+    "eig_resid_mv8": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "eig_dot_diag_mv8": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "eig_gram_mv8": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "eig_orthonormalize_mv8": (_int, [_vp, _i64, _i64, _vp, _int]),
@@ -641,6 +642,11 @@ def spmm_blk_mv8(A, m, Qin, Qout):
     A.ctx.check(lib.eig_spmm_blk_mv8(A.h, m, Qin.ptr, Qout.ptr))
 
 
+def resid_mv8(A, m, X, B, R):
+    """eig_resid_mv8: R = B - A X in one pass, square blocks 1..4 (R may be B, never X)."""
+    A.ctx.check(lib.eig_resid_mv8(A.h, m, X.ptr, B.ptr, R.ptr))
+
+
 def dot_diag_mv8(ctx, n, m, Q1, Q2, dp):
     ctx.check(lib.eig_dot_diag_mv8(ctx.h, n, m, Q1.ptr, Q2.ptr, dp.ptr))
 
@@ -979,7 +985,9 @@ def arnoldi_shift_invert(A, nev, sigma=0.0, B=None, mode="std", ncv=0, tol=0.0, 
 
 
 class Multigrid:
-    """eig_mg_t: geometric multigrid on a box-grid matrix (include/eigmi.h eig_mg_create)."""
+    """eig_mg_t: geometric multigrid on a box-grid matrix (include/eigmi.h eig_mg_create).  1x1 blocks, or square
+    blocks b = 2..4 (block-Jacobi smoothing): dims are the node extents (their product = A's block rows), the
+    multivectors of solve have A.info.n = nb_rows * b scalar rows and info()'s coarse_rows are scalar rows."""
 
     def __init__(self, A, dims, max_cols=32, smooth_degree=2, smooth_ratio=10.0):
         self.A = A
@@ -1014,7 +1022,7 @@ class Multigrid:
 
 class BlockLanczos:
     """eig_blanczos_t: block Lanczos for K x = lambda M x (config C5), see include/eigmi.h.
-    K, M (and Ks): 1x1 blocks, or the same square blocks b = 2..4 on one rank (not with mg): vectors
+    K, M (and Ks): 1x1 blocks, or the same square blocks b = 2..4 on one rank (also with mg): vectors
     have K.info.n = nb_rows * b scalar rows, the Chebyshev solve is point Jacobi on the scalar diagonal
     of the diagonal blocks; other block shapes raise EigShapeError (EIG_ERR_BLOCKSIZE)."""
 

@@ -361,6 +361,11 @@ int eig_spmm_mv8(eig_mat_t mat, int64_t m, const double *Qin, double *Qout);
  * on the matrix's scalar expansion (per row: stored blocks in order, c = 0..br-1 inside a block).
  * Rectangular blocks: EIG_ERR_BLOCKSIZE. */
 int eig_spmm_blk_mv8(eig_mat_t mat, int64_t m, const double *Qin, double *Qout);
+/* R = B - A X in one pass (the residual epilogue of the product), m columns (m % 8 == 0), for a square
+ * matrix on one rank with 1x1 blocks or square blocks b = 2..4 (n = nb_rows * b scalar rows).  On blocks the
+ * row sums are eig_spmm_blk_mv8's, so R is bitwise B minus that product.  R may alias B, never X
+ * (EIG_ERR_ARG).  Rectangular blocks: EIG_ERR_BLOCKSIZE. */
+int eig_resid_mv8(eig_mat_t A, int64_t m, const double *X, const double *B, double *R);
 /* a5: dp[j] = q1_j . q2_j, j < m (kernels_cpp.hh:24-55).  dp: device, m doubles. */
 int eig_dot_diag_mv8(eig_ctx_t ctx, int64_t n, int64_t m, const double *Q1, const double *Q2, double *dp);
 /* a6: G = Q1^T Q2 (m1 x m2, row-major, device) -- the tall-skinny panel product, on MFMA
@@ -658,7 +663,8 @@ int eig_arnoldi_shift_invert(eig_mat_t A, eig_mat_t B, eig_lu_t lu, double sigma
  * vector then has n = nb_rows * b scalar rows (the (max_steps + 1) * block <= n check, the start block,
  * eig_blanczos_ritz's vectors), the products run on the blocked image, and the Chebyshev-Jacobi solve
  * is POINT Jacobi: D is the scalar diagonal of the diagonal blocks, so [lmin, lmax] bound the spectrum
- * of that D^-1 M (D^-1 Ks).  eig_blanczos_create_si_mg stays 1x1 (eig_mg_create refuses blocks).
+ * of that D^-1 M (D^-1 Ks).  eig_blanczos_create_si_mg takes the same blocks with a multigrid built on
+ * the blocked Ks (eig_mg_create; block-Jacobi smoothing there).
  * The start block is mt19937(seed) normal numbers in MultiVector fill order over the global scalar
  * rows (eigensolver.hh:49-55). */
 typedef struct eig_blanczos_s *eig_blanczos_t;
@@ -689,8 +695,16 @@ int eig_blanczos_create_si(eig_mat_t K, eig_mat_t M, eig_mat_t Ks, double sigma,
  * Kuhn stencils): coarse grids keep the nodes of odd index per direction, trilinear P, Galerkin
  * P^T A P on the host (27-point, bitwise symmetric), Chebyshev-Jacobi smoothing of degree
  * smooth_degree on [lmax / smooth_ratio, lmax] (lmax = Gershgorin bound of diag(A)^-1 A), the
- * coarsest level (<= 64 rows) solved to 1e-15 by Chebyshev on its exact spectrum.  max_cols: the
- * widest multivector a solve takes (workspace: 6 x rows x max_cols doubles per level). */
+ * coarsest level (<= 64 nodes) solved to 1e-15 by Chebyshev on its exact spectrum.  max_cols: the
+ * widest multivector a solve takes (workspace: 6 x rows x max_cols doubles per level).
+ * Square blocks FieldMatrix<double,b,b>, b = 2..4, on one rank as well (e.g. Q1 elasticity): the grid is
+ * the grid of NODES, nx * ny * nz = nb_rows (else EIG_ERR_SHAPE), vectors have n = nb_rows * b scalar rows
+ * (node-major), P = P_trilinear (x) I_b, the Galerkin operator has a b x b block per stencil slot, and the
+ * smoother is Chebyshev with BLOCK Jacobi: D the block diagonal (its blocks must be positive definite, else
+ * EIG_ERR_BREAKDOWN), lmax = max_I sum_J ||L_I^-1 A_IJ L_J^-T||_2 with D_I = L_I L_I^T.  Rectangular
+ * blocks: EIG_ERR_BLOCKSIZE; a distributed context, or a matrix that couples nodes more than one grid step
+ * apart: EIG_ERR_ARG.  eig_mg_info's coarse_rows are scalar rows (nodes * b) and eig_mg_solve's multivectors
+ * have n = nb_rows * b rows. */
 typedef struct eig_mg_s *eig_mg_t;
 int eig_mg_create(eig_mat_t A, int nx, int ny, int nz, int max_cols, int smooth_degree, double smooth_ratio,
                   eig_mg_t *mg);
@@ -764,7 +778,7 @@ int eig_lobpcg_create(eig_mat_t K, eig_mat_t M, int block, int which, const doub
                       eig_lobpcg_t *ws);
 /* T = `degree` Chebyshev-Jacobi steps on the SPD matrix Ap (NULL: K; blocks as K's, point Jacobi on blocks
  * as in eig_mass_solve_mv8) with the spectrum of diag(Ap)^-1 Ap in [lmin, lmax].  T = `cycles` multigrid
- * iterations (mg of K's context and size, max_cols >= block, else EIG_ERR_ARG; 1x1 blocks).  Without
+ * iterations (mg of K's context and size, max_cols >= block, else EIG_ERR_ARG; blocks as K's).  Without
  * either call T = I.  A preconditioner with EIG_WHICH_LA: EIG_ERR_ARG. */
 int eig_lobpcg_precond_cheb(eig_lobpcg_t ws, eig_mat_t Ap, int degree, double lmin, double lmax);
 int eig_lobpcg_precond_mg(eig_lobpcg_t ws, eig_mg_t mg, int cycles);

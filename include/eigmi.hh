@@ -612,10 +612,55 @@ void computeGenNonSymShiftInvertMinMagnitude(const Matrix &A, const Matrix &B, d
   detail::nonsym(A, B, epsilon, x, lambda, sigma, EIG_ARNOLDI_GEN, maxit);
 }
 
+// --------------------------------------------------------------------------------- multigrid
+// Geometric multigrid on a box-grid matrix (eig_mg_*, include/eigmi.h): 1x1 blocks, or square blocks
+// FieldMatrix<double,b,b>, b = 2..4, with block-Jacobi smoothing; nx x ny x nz are the NODE extents
+// (nx ny nz = A's block rows) and multivectors have A.info().n = block rows * b scalar rows.  The matrix must
+// outlive the hierarchy.
+class Multigrid {
+ public:
+  struct Info {
+    int levels;
+    int64_t coarse_rows;  // scalar rows of the coarsest level
+    int coarse_degree;
+    double lmax_fine;
+  };
+  Multigrid(const Matrix &A, int nx, int ny, int nz, int max_cols = 32, int smooth_degree = 2,
+            double smooth_ratio = 10.0)
+      : ctx_(A.ctx())
+  {
+    check(eig_mg_create(A.get(), nx, ny, nz, max_cols, smooth_degree, smooth_ratio, &h_), ctx_);
+  }
+  Multigrid(const Multigrid &) = delete;
+  Multigrid &operator=(const Multigrid &) = delete;
+  ~Multigrid() { eig_mg_destroy(h_); }
+  Info info() const
+  {
+    Info i{};
+    check(eig_mg_info(h_, &i.levels, &i.coarse_rows, &i.coarse_degree, &i.lmax_fine), ctx_);
+    return i;
+  }
+  // X = S_cycles B on device multivectors (distinct buffers, cols() <= max_cols); returns max_j ||B - A X|| /
+  // ||B|| when want_resid, else 0
+  double solve(const DeviceMultiVector &B, DeviceMultiVector &X, int cycles, bool want_resid = false) const
+  {
+    if (B.rows() != X.rows() || B.cols() != X.cols())
+      throw std::invalid_argument("eigmi::Multigrid::solve: B and X differ in shape");
+    double r = 0.0;
+    check(eig_mg_solve(h_, (int64_t)B.cols(), B.data(), X.data(), cycles, want_resid ? &r : nullptr), ctx_);
+    return r;
+  }
+  eig_mg_t get() const { return h_; }
+
+ private:
+  eig_ctx_t ctx_;
+  eig_mg_t h_ = nullptr;
+};
+
 // ------------------------------------------------------------------------------------ LOBPCG
 // K x = lambda M x (M = nullptr: K x = lambda x) by LOBPCG (eig_lobpcg_*, include/eigmi.h): the smallest
-// end with an optional Chebyshev-Jacobi preconditioner, or the largest end without one.  The matrices
-// must outlive the solver.
+// end with an optional Chebyshev-Jacobi or multigrid preconditioner, or the largest end without one.  The
+// matrices (and a multigrid) must outlive the solver.
 class Lobpcg {
  public:
   Lobpcg(const Matrix &K, const Matrix *M, int block, int which = EIG_WHICH_SA, unsigned seed = 123,
@@ -632,6 +677,8 @@ class Lobpcg {
   {
     check(eig_lobpcg_precond_cheb(h_, Ap ? Ap->get() : nullptr, degree, lmin, lmax), ctx_);
   }
+  // `cycles` multigrid iterations (mg built on K, max_cols >= block)
+  void precond_mg(const Multigrid &mg, int cycles = 1) { check(eig_lobpcg_precond_mg(h_, mg.get(), cycles), ctx_); }
   // up to max_iters iterations; true when the first nev pairs hold ||K x - theta M x|| <= tol theta ||M x||
   bool step(int max_iters, int nev, double tol, int *iters_done = nullptr, eig_lobpcg_timing *timing = nullptr)
   {

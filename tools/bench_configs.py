@@ -17,6 +17,10 @@
       12 nnz + 4 (n+1) + (32 m + 8) n bytes per m-column launch (EIGMI_C5_N, default 256)
   LOBPCG  the smallest end of the C5 pencil by LOBPCG with one multigrid V-cycle per iteration, its two
       streaming kernels alone, the fused update A/B against four panel updates, and c5si beside it
+  MGBLK  the blocked multigrid on the C3 matrix (q1elast 64^3, 3x3): setup, one V-cycle at m = 8 and 32, the
+      blocked residual and the point Chebyshev step beside the same run's blocked product (interleaved), and
+      LOBPCG block 32 on the C3 pencil with one V-cycle against Chebyshev-Jacobi degree 4; mgblk_stats turns
+      the kernel-trace summary of that run into one line per blocked kernel (block-Jacobi step, transfers)
 
 One JSON line per measurement; algorithmic bytes per SURVEY 8(d); peak 8 TB/s.
 """
@@ -728,7 +732,102 @@ def lobpcg(ctx):
     c5si(ctx)
 
 
+def mgblk(ctx):
+    """The blocked multigrid at C3 size: K = q1elast(64) (3x3 blocks, 262,144 nodes), the pencil's M of c3_pencil.
+    Hierarchy setup (host Galerkin, block inverses, block Gershgorin bounds, uploads); one V-cycle
+    (eig_mg_solve, cycles = 1, smoother degree 2, ratio 5) at m = 8 and 32 with the residual after 1 and 8
+    cycles; the blocked product, the blocked residual (eig_resid_mv8) and the point Chebyshev step (two solve
+    degrees' difference) interleaved over five rounds; LOBPCG block 32, nev 8, tol 1e-8 with one V-cycle and with
+    Chebyshev-Jacobi degree 4 on [g / 10, g] (at most EIGMI_MGBLK_ITERS = 300 iterations each; 0 skips it).  The
+    block-Jacobi step and the two transfers have no entry point of their own: their times come from kernel
+    traces of this config at one width each (EIGMI_MGBLK_M = 8 or 32, EIGMI_MGBLK_ITERS = 0; tools/gpu.sh mgblk,
+    mgblk_stats below)."""
+    N = int(os.environ.get("EIGMI_MGBLK_N", "64"))
+    cfg = f"C3 Q1 elasticity {N}^3 3x3 BCSR, blocked multigrid"
+    rp, c, v = eigmi.gen_matrix(eigmi.GEN_Q1ELAST3D, N)
+    nb, n = N ** 3, 3 * N ** 3
+    K = eigmi.Matrix.from_bcsr(ctx, rp, c, v, 3, 3)
+    t0 = time.perf_counter()
+    mg = eigmi.Multigrid(K, (N, N, N), max_cols=32, smooth_degree=2, smooth_ratio=5.0)
+    emit(config=cfg, op="hierarchy setup (host Galerkin + block Jacobi data + uploads)",
+         s=round(time.perf_counter() - t0, 2), mg=mg.info())
+    v3 = v.reshape(-1, 3, 3)
+    g = float((np.add.reduceat(np.abs(v3).sum(axis=2), rp[:-1], axis=0) / (16.0 / 3.0)).max())
+    for m in [int(x) for x in os.environ.get("EIGMI_MGBLK_M", "8,32").split(",")]:
+        B, X, R = ctx.array(oracle.random_mv8(n, m, 2)), ctx.zeros(n * m), ctx.zeros(n * m)
+        r1 = mg.solve(m, B, X, 1, resid=True)
+        r8 = mg.solve(m, B, X, 8, resid=True)
+        tv = min(wall(lambda: mg.solve(m, B, X, 1), 10)[0] for _ in range(3))
+        t3 = min(wall(lambda: mg.solve(m, B, X, 3), 5)[0] for _ in range(3))
+        emit(config=cfg, op=f"one V-cycle m={m} (eig_mg_solve, cycles = 1, synchronous)", us=round(tv * 1e6, 1),
+             three_cycles_us=round(t3 * 1e6, 1), residual_after_1=r1, residual_after_8=r8,
+             contraction_per_cycle=round((r8 / r1) ** (1.0 / 7.0), 4))
+
+        def batch(f, reps=20):
+            t = time.perf_counter()
+            for _ in range(reps):
+                f()
+            ctx.sync()
+            return (time.perf_counter() - t) / reps * 1e6
+        d0, d1 = 2, 12
+        rounds = {"spmm": [], "resid": [], "cheb_point": []}
+        eigmi.spmm_blk_mv8(K, m, B, R), eigmi.resid_mv8(K, m, B, X, R), eigmi.mass_solve_mv8(K, m, d1, B, X, g / 10, g)
+        ctx.sync()
+        for _ in range(5):
+            rounds["spmm"].append(batch(lambda: eigmi.spmm_blk_mv8(K, m, B, R)))
+            rounds["resid"].append(batch(lambda: eigmi.resid_mv8(K, m, B, X, R)))
+            a = batch(lambda: eigmi.mass_solve_mv8(K, m, d0, B, X, g / 10, g), 5)
+            b = batch(lambda: eigmi.mass_solve_mv8(K, m, d1, B, X, g / 10, g), 5)
+            rounds["cheb_point"].append((b - a) / (d1 - d0))
+        emit(config=cfg, op=f"blocked product / residual / point Chebyshev step m={m} (interleaved, 5 rounds)",
+             **{k + "_us": [round(x, 1) for x in r] for k, r in rounds.items()},
+             **{k + "_median_us": round(float(np.median(r)), 1) for k, r in rounds.items()})
+        B.free(), X.free(), R.free()
+    # the C3 pencil (c3_pencil's M = D + 0.3 (K - D)), LOBPCG block 32
+    dg = np.nonzero(c == np.repeat(np.arange(nb), np.diff(rp)))[0][:, None]
+    r = np.arange(3)
+    vm = 0.3 * v3
+    vm[dg, r, r] = v3[dg, r, r]
+    M = eigmi.Matrix.from_bcsr(ctx, rp, c, vm.reshape(-1), 3, 3)
+    b, nev, tol, cap = 32, 8, 1e-8, int(os.environ.get("EIGMI_MGBLK_ITERS", "300"))
+    for name in ("one V-cycle", "Chebyshev-Jacobi degree 4") if cap > 0 else ():
+        s = eigmi.Lobpcg(K, M, block=b, seed=123)
+        if name == "one V-cycle":
+            s.precond_mg(mg, 1)
+        else:
+            s.precond_cheb(4, g / 10.0, g)
+        tw, (it, conv, t) = wall(lambda: s.step(cap, nev, tol))
+        ev, _, res = s.ritz(nev)
+        emit(config=cfg + f", LOBPCG block {b}, nev {nev}, tol {tol:g}", op=name, iterations=it, converged=conv,
+             device_ms=round(t.total_ms, 1), ms_per_iteration=round(t.total_ms / max(it, 1), 2),
+             precond_ms_per_iteration=round(t.precond_ms / max(it, 1), 2), wall_s=round(tw, 2),
+             eigenvalues=[float(x) for x in ev], relative_residuals=[float(a / abs(e)) for a, e in zip(res, ev)])
+        s.close()
+    mg.close()
+    K.close(), M.close()
+
+
+def mgblk_stats(path, m):
+    """The fine-level launches of the blocked multigrid's kernels in a rocprofv3 --kernel-trace of mgblk at one
+    width m: per kernel the dispatches with the largest grid (the 64^3 level), their count, median and minimum."""
+    import csv
+    keys = ("k_spmm_blk_mv8", "k_cheb_init_bjac", "k_mg_restrict", "k_mg_prolong", "k_mv8_axpby")
+    runs = {}
+    for r in csv.DictReader(open(path)):
+        name = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("eigmi::", "")
+        if any(k in name for k in keys):
+            grid = int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"])
+            runs.setdefault(name, {}).setdefault(grid, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for name, by_grid in sorted(runs.items()):
+        t = by_grid[max(by_grid)]
+        emit(m=int(m), kernel=name, level="fine (largest grid)", calls=len(t), median_us=round(float(np.median(t)), 2),
+             min_us=round(min(t), 2), max_us=round(max(t), 2))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["mgblk_stats"]:
+        mgblk_stats(sys.argv[2], sys.argv[3])
+        sys.exit(0)
     ctx = eigmi.Context(0)
     which = sys.argv[1:] or ["c1", "c2", "c3", "inv"]
     for w in which:

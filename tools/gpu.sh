@@ -21,6 +21,8 @@
 #   c5trace              both under a kernel trace                            -> c5_trace/, c5si_trace/
 #   lobpcg | lobpcgtrace LOBPCG on the variable-coefficient C5 pencil 256^3 (one V-cycle), its kernels' A/B and
 #                        c5si in one process; the same under a kernel trace   -> lobpcg.jsonl, lobpcg_trace/
+#   mgblk                the blocked multigrid at C3 size (q1elast 64^3, 3x3): V-cycle, residual / Chebyshev A/B, LOBPCG
+#                        with one V-cycle vs Chebyshev degree 4; then the same under a kernel trace -> mgblk.jsonl, mgblk_kernels.jsonl
 #   latency              fused step vs eig_mv across sizes and slabs, plane-run counts  -> latency.jsonl
 #   marchcopy            the march streams alone (tools/march_copy.hip)       -> march_copy.jsonl
 #   prefetch             geometric march prefetch variants x plane runs (256^3, 128^3, slab) -> latency.jsonl
@@ -125,6 +127,17 @@ run_task() {
       EIGMI_C5_N=256 timeout -k 10 600 python -u tools/bench_configs.py c5si > "$O/c5si.jsonl" 2> "$O/c5si.err" ;;
     lobpcg)
       EIGMI_C5_N=256 EIGMI_C5_VAR=1 timeout -k 10 900 python -u tools/bench_configs.py lobpcg > "$O/lobpcg.jsonl" 2> "$O/lobpcg.err" ;;
+    mgblk)
+      # plain run for the wall-clock numbers, then a kernel trace per width for the per-kernel times (the
+      # block-Jacobi step, the blocked residual and the transfers beside k_spmm_blk_mv8 in one process)
+      prof_env
+      timeout -k 10 500 python -u tools/bench_configs.py mgblk > "$O/mgblk.jsonl" 2> "$O/mgblk.err" || return 1
+      : > "$O/mgblk_kernels.jsonl"
+      for m in 8 32; do
+        EIGMI_MGBLK_M=$m EIGMI_MGBLK_ITERS=0 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$O/mgblk_trace$m" -o trace -- \
+          python3 tools/bench_configs.py mgblk > "$O/mgblkt$m.jsonl" 2> "$O/mgblkt$m.err" || return 1
+        python3 tools/bench_configs.py mgblk_stats "$(find "$O/mgblk_trace$m" -name '*kernel_trace.csv' | head -1)" $m >> "$O/mgblk_kernels.jsonl" || return 1
+      done ;;
     lobpcgtrace)
       # the same under a kernel trace: k_lobpcg_update / k_lobpcg_resid and the rest of an iteration per kernel
       prof_env
