@@ -16,6 +16,12 @@
 // k_spmm_blk_mv8_cheb<.., true>), lmax the block Gershgorin bound max_I sum_J ||L_I^-1 A_IJ L_J^-T||_2,
 // D_I = L_I L_I^T.  Point Jacobi ignores the coupling inside a node and contracts half as fast.
 //
+// Algebraic hierarchies (eig_amg_create; 1x1 blocks, any pattern, no grid): amg_setup.h / amg_setup.cpp build
+// every level on the host from the matrix alone -- strength of connection, three-pass aggregation, the smoothed
+// prolongator P = (I - omega D^-1 A) T and its transpose, A_c = P^T (A P) mirrored -- and a level carries the device
+// CSR of P and P^T for the transfers of k_amg.hip instead of grid extents.  The V-cycle below is the same one:
+// vcycle() only picks the transfers by the level's kind.
+//
 // Solve (device, no reductions): X = S_k B with S_k = sum_{i<k} (I - V A)^i V, i.e. `cycles`
 // stationary iterations x += V (b - A x) from x = 0, V one symmetric V-cycle:
 //   pre-smooth  x = p(D^-1 A) D^-1 b      (Chebyshev-Jacobi, degree nu, on [lmax / ratio, lmax],
@@ -31,6 +37,7 @@
 #include <thread>
 #include <vector>
 
+#include "amg_setup.h"
 #include "internal.h"
 #include "mg_setup.h"
 
@@ -43,7 +50,36 @@ void launch_mg_restrict(const int *fdim, const int *cdim, int b, i64 m, i64 ldf,
 void launch_mg_prolong_add(const int *fdim, const int *cdim, int b, i64 m, i64 ldf, i64 ldc, const double *Xc,
                            double *Xf, hipStream_t s);
 void launch_mv8_axpby(i64 n, i64 m, i64 ld, double a, const double *X, double b, double *Y, hipStream_t s);
+// transfers of an algebraic hierarchy on the device CSR of P^T (cn rows) / P (fn rows) (k_amg.hip)
+void launch_amg_restrict(i64 cn, const i64 *rp, const i32 *col, const double *val, i64 m, i64 ldf, i64 ldc,
+                         const double *Rf, double *Bc, hipStream_t s);
+void launch_amg_prolong_add(i64 fn, const i64 *rp, const i32 *col, const double *val, i64 m, i64 ldf, i64 ldc,
+                            const double *Xc, double *Xf, hipStream_t s);
 }  // namespace eigmi
+
+// Device CSR of a transfer operator (row pointers i64, columns i32, values double).
+struct AmgCsrDev {
+  DevBuf *rp = nullptr, *col = nullptr, *val = nullptr;
+  void upload(const MgCsr &h)
+  {
+    rp = new DevBuf(h.rp.size() * sizeof(i64));
+    col = new DevBuf(h.col.size() * sizeof(i32));
+    val = new DevBuf(h.val.size() * sizeof(double));
+    EIG_HIP(hipMemcpy(rp->p, h.rp.data(), h.rp.size() * sizeof(i64), hipMemcpyHostToDevice));
+    if (!h.col.empty())
+    {
+      EIG_HIP(hipMemcpy(col->p, h.col.data(), h.col.size() * sizeof(i32), hipMemcpyHostToDevice));
+      EIG_HIP(hipMemcpy(val->p, h.val.data(), h.val.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+  }
+  void release()
+  {
+    delete rp;
+    delete col;
+    delete val;
+    rp = col = val = nullptr;
+  }
+};
 
 struct MgLevel {
   eig_mat_s *A = nullptr;
@@ -51,6 +87,11 @@ struct MgLevel {
   int dim[3] = {0, 0, 0};                     // nodes per direction
   int b = 1;                                  // scalar rows per node (the block size)
   i64 n = 0;                                  // scalar rows (nodes * b)
+  i64 nnz = 0;                                // stored scalar entries of A
+  // algebraic hierarchy (eig_amg_create): the transfers to the next level, P (n rows) and P^T (rows of the next
+  // level); a geometric level has none and uses dim[]
+  bool algebraic = false;
+  AmgCsrDev P, PT;
   double lmax = 2.0;                          // (block) Gershgorin bound of D^-1 A
   double clo = 0.0, chi = 0.0;                // coarsest: exact spectrum bounds of D^-1 A
   int cdeg = 0;                               // coarsest: Chebyshev degree
@@ -68,6 +109,8 @@ struct eig_mg_s {
     for (auto &L : lev)
     {
       for (DevBuf *b : {L.dinv, L.B, L.T, L.C[0], L.C[1], L.C[2], L.C[3]}) delete b;
+      L.P.release();
+      L.PT.release();
       if (L.own && L.A) eig_mat_destroy(L.A);
     }
   }
@@ -128,9 +171,17 @@ double *vcycle(eig_mg_s &mg, size_t l, i64 m, const double *b)
   double *x = smooth(L, m, mg.nu, lo, hi, b, C[0], C[1], C[2], s);
   double *T = L.T->d();
   launch_resid_mv8(*L.A, m, x, b, T, s);  // T = b - A x
-  launch_mg_restrict(L.dim, Cl.dim, L.b, m, L.n, Cl.n, T, Cl.B->d(), s);
+  if (L.algebraic)
+    launch_amg_restrict(Cl.n, (const i64 *)L.PT.rp->p, (const i32 *)L.PT.col->p, (const double *)L.PT.val->p, m, L.n, Cl.n,
+                        T, Cl.B->d(), s);
+  else
+    launch_mg_restrict(L.dim, Cl.dim, L.b, m, L.n, Cl.n, T, Cl.B->d(), s);
   const double *xc = vcycle(mg, l + 1, m, Cl.B->d());
-  launch_mg_prolong_add(L.dim, Cl.dim, L.b, m, L.n, Cl.n, xc, x, s);
+  if (L.algebraic)
+    launch_amg_prolong_add(L.n, (const i64 *)L.P.rp->p, (const i32 *)L.P.col->p, (const double *)L.P.val->p, m, L.n, Cl.n, xc,
+                           x, s);
+  else
+    launch_mg_prolong_add(L.dim, Cl.dim, L.b, m, L.n, Cl.n, xc, x, s);
   launch_resid_mv8(*L.A, m, x, b, T, s);  // T = b - A x
   // x += post-smoothing correction: a degree-2 smoother on the row-class image adds its x_2 in
   // place (cheb_solve's first step, its gamma and omega_1); 1x1 blocks only
@@ -235,6 +286,7 @@ extern "C" int eig_mg_create(eig_mat_t A, int nx, int ny, int nz, int max_cols, 
       {
         MgLevel &F = mg->lev.back();
         const i64 nodes = F.n / bs;
+        F.nnz = (i64)h.col.size() * bs * bs;
         if (bs == 1)
         {
           F.lmax = mg_gershgorin(h, F.n);
@@ -278,6 +330,143 @@ extern "C" int eig_mg_create(eig_mat_t A, int nx, int ny, int nz, int max_cols, 
       throw;
     }
     *out = mg;
+  });
+}
+
+extern "C" int eig_amg_create(eig_mat_t A, double theta, int max_cols, int smooth_degree, double smooth_ratio,
+                              eig_mg_t *out)
+{
+  return guard(A ? A->ctx : nullptr, [&] {
+    EIG_CHECK(A && out && theta >= 0.0 && max_cols >= 8 && max_cols % 8 == 0 && smooth_degree >= 1 && smooth_ratio > 1.0,
+              EIG_ERR_ARG, "eig_amg_create: bad argument");
+    EIG_CHECK(A->br == 1 && A->bc == 1, EIG_ERR_BLOCKSIZE,
+              "eig_amg_create: 1x1 blocks only (blocked matrices need their near-null-space)");
+    EIG_CHECK(!A->ctx->distributed() && A->nb_rows == A->nb_cols && A->window == A->nb_rows && A->nb_rows >= 1,
+              EIG_ERR_ARG, "eig_amg_create: square single-rank matrix required");
+    eig_ctx_t ctx = A->ctx;
+    EIG_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // the whole hierarchy on the host first (amg_setup.cpp; a refusal leaves nothing on the device)
+    AmgHierarchy H;
+    {
+      MgCsr h;
+      mat_download_bcsr(*A, h.rp, h.col, h.val);
+      amg_build(std::move(h), A->nb_rows, theta, H);
+    }
+    auto *mg = new eig_mg_s();
+    try
+    {
+      mg->ctx = ctx;
+      mg->max_cols = max_cols;
+      mg->nu = smooth_degree;
+      mg->ratio = smooth_ratio;
+      const size_t nl = H.A.size();
+      mg->lev.reserve(nl);
+      for (size_t l = 0; l < nl; ++l)
+      {
+        mg->lev.emplace_back();
+        MgLevel &L = mg->lev.back();
+        L.n = H.rows[l];
+        L.nnz = (i64)H.A[l].col.size();
+        L.lmax = H.lmax[l];
+        L.algebraic = true;
+        if (l == 0)
+          L.A = A;
+        else
+        {
+          eig_mat_t Ac = nullptr;
+          const int rc = eig_mat_create_bcsr(ctx, L.n, L.n, 1, 1, H.A[l].rp.data(), H.A[l].col.data(), H.A[l].val.data(), &Ac);
+          if (rc != EIG_OK) throw Error(rc, std::string("algebraic multigrid: coarse upload: ") + eig_last_error(ctx));
+          L.A = Ac;
+          L.own = true;
+        }
+        alloc_level(L, max_cols, s);
+        launch_diag_inv(*L.A, L.dinv->d(), s);
+        if (l + 1 < nl)
+        {
+          L.P.upload(H.P[l]);
+          L.PT.upload(H.PT[l]);
+        }
+        else
+        {
+          L.clo = H.clo;
+          L.chi = H.chi;
+          L.cdeg = H.cdeg;
+        }
+      }
+      EIG_HIP(hipStreamSynchronize(s));
+    }
+    catch (...)
+    {
+      delete mg;
+      throw;
+    }
+    *out = mg;
+  });
+}
+
+extern "C" int eig_amg_aggregate(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, double theta_l,
+                                 int64_t *agg, int64_t *naggregates)
+{
+  return guard(nullptr, [&] {
+    EIG_CHECK(n >= 0 && rowptr && agg && naggregates && theta_l >= 0.0 && (n == 0 || rowptr[n] == 0 || (col && val)),
+              EIG_ERR_ARG, "eig_amg_aggregate: bad argument");
+    for (i64 i = 0; i < n; ++i)
+    {
+      EIG_CHECK(rowptr[i] <= rowptr[i + 1], EIG_ERR_ARG, "eig_amg_aggregate: row pointers must ascend");
+      for (i64 k = rowptr[i]; k < rowptr[i + 1]; ++k)
+        EIG_CHECK(col[k] >= 0 && col[k] < n, EIG_ERR_SHAPE, "eig_amg_aggregate: column out of range");
+    }
+    std::vector<i64> a;
+    *naggregates = amg_aggregate(n, rowptr, col, val, theta_l, a);
+    std::copy(a.begin(), a.end(), agg);
+  });
+}
+
+extern "C" int eig_amg_transfer_mv8(eig_ctx_t ctx, int add, int64_t nrows, int64_t ncols, const int64_t *rowptr,
+                                    const int32_t *col, const double *val, int64_t m, const double *In, double *Out)
+{
+  return guard(ctx, [&] {
+    EIG_CHECK(ctx && rowptr && In && Out && nrows >= 1 && ncols >= 1 && m > 0 && m % 8 == 0 && m <= 32 && rowptr[0] == 0 &&
+                  (rowptr[nrows] == 0 || (col && val)),
+              EIG_ERR_ARG, "eig_amg_transfer_mv8: bad argument");
+    MgCsr h;
+    h.rp.assign(rowptr, rowptr + nrows + 1);
+    for (i64 i = 0; i < nrows; ++i) EIG_CHECK(h.rp[i] <= h.rp[i + 1], EIG_ERR_ARG, "eig_amg_transfer_mv8: row pointers must ascend");
+    h.col.assign(col, col + h.rp[nrows]);
+    h.val.assign(val, val + h.rp[nrows]);
+    for (i32 c : h.col) EIG_CHECK(c >= 0 && c < ncols, EIG_ERR_SHAPE, "eig_amg_transfer_mv8: column out of range");
+    EIG_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    AmgCsrDev d;
+    try
+    {
+      d.upload(h);
+      if (add)
+        launch_amg_prolong_add(nrows, (const i64 *)d.rp->p, (const i32 *)d.col->p, (const double *)d.val->p, m, nrows, ncols,
+                               In, Out, s);
+      else
+        launch_amg_restrict(nrows, (const i64 *)d.rp->p, (const i32 *)d.col->p, (const double *)d.val->p, m, ncols, nrows, In,
+                            Out, s);
+      EIG_HIP(hipStreamSynchronize(s));
+    }
+    catch (...)
+    {
+      d.release();
+      throw;
+    }
+    d.release();
+  });
+}
+
+extern "C" int eig_mg_level_info(eig_mg_t mg, int level, int64_t *rows, int64_t *nnz, double *lmax)
+{
+  return guard(mg ? mg->ctx : nullptr, [&] {
+    EIG_CHECK(mg && level >= 0 && level < (int)mg->lev.size(), EIG_ERR_ARG, "eig_mg_level_info: no such level");
+    const MgLevel &L = mg->lev[level];
+    if (rows) *rows = L.n;
+    if (nnz) *nnz = L.nnz;
+    if (lmax) *lmax = L.lmax;
   });
 }
 

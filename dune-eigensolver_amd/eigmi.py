@@ -208,6 +208,10 @@ SIGNATURES = {
                            ctypes.POINTER(_dbl)]),
     "eig_mg_solve": (_int, [_vp, _i64, _vp, _vp, _int, ctypes.POINTER(_dbl)]),
     "eig_mg_destroy": (_int, [_vp]),
+    "eig_amg_create": (_int, [_vp, _dbl, _int, _int, _dbl, ctypes.POINTER(_vp)]),
+    "eig_mg_level_info": (_int, [_vp, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_dbl)]),
+    "eig_amg_aggregate": (_int, [_i64, _vp, _vp, _vp, _dbl, _vp, ctypes.POINTER(_i64)]),
+    "eig_amg_transfer_mv8": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "eig_blanczos_create_si_mg": (_int, [_vp, _vp, _vp, _dbl, _vp, _int, _int, _int, _u, ctypes.POINTER(_vp)]),
     "eig_blanczos_ritz": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "eig_blanczos_tmatrix": (_int, [_vp, ctypes.POINTER(_int), _vp]),
@@ -997,6 +1001,31 @@ class Multigrid:
         self.h = h
         _track(self)
 
+    @classmethod
+    def amg(cls, A, theta=0.08, max_cols=32, smooth_degree=2, smooth_ratio=5.0):
+        """Smoothed-aggregation algebraic multigrid on a square single-rank SPD matrix with 1x1 blocks and any
+        pattern (eig_amg_create); theta: the strength threshold of level 0, halved per level.  The defaults are
+        those of the sweep in DESIGN.md 4d."""
+        self = cls.__new__(cls)
+        self.A = A
+        self.h = None
+        h = _vp()
+        A.ctx.check(lib.eig_amg_create(A.h, theta, max_cols, smooth_degree, smooth_ratio, ctypes.byref(h)))
+        self.h = h
+        _track(self)
+        return self
+
+    def level_info(self, level):
+        """{"rows", "nnz", "lmax"} of one level (0 = the matrix itself), for either kind of hierarchy."""
+        r, z, lm = _i64(0), _i64(0), _dbl(0)
+        self.A.ctx.check(lib.eig_mg_level_info(self.h, level, ctypes.byref(r), ctypes.byref(z), ctypes.byref(lm)))
+        return {"rows": r.value, "nnz": z.value, "lmax": lm.value}
+
+    def complexity(self):
+        """Operator complexity: the levels' stored entries over the fine matrix's."""
+        z = [self.level_info(l)["nnz"] for l in range(self.info()["levels"])]
+        return sum(z) / z[0]
+
     def info(self):
         lv, cr, cd, lm = _int(0), _i64(0), _int(0), _dbl(0)
         self.A.ctx.check(lib.eig_mg_info(self.h, ctypes.byref(lv), ctypes.byref(cr), ctypes.byref(cd), ctypes.byref(lm)))
@@ -1213,6 +1242,30 @@ def reorder_rcm(rowptr, col):
     if rc != EIG_OK:
         raise EigError(rc, lib.eig_last_error(None).decode())
     return perm
+
+
+def amg_aggregate(rowptr, col, vals, theta_l):
+    """The aggregation of eig_amg_create at one level (eig_amg_aggregate, host-only): (agg[n], naggregates)."""
+    rowptr = np.ascontiguousarray(rowptr, np.int64)
+    col = np.ascontiguousarray(col, np.int32)
+    vals = np.ascontiguousarray(vals, np.float64)
+    agg = np.zeros(rowptr.size - 1, np.int64)
+    na = _i64(0)
+    rc = lib.eig_amg_aggregate(rowptr.size - 1, _np_ptr(rowptr), _np_ptr(col), _np_ptr(vals), theta_l, _np_ptr(agg),
+                               ctypes.byref(na))
+    if rc != EIG_OK:
+        raise EigError(rc, lib.eig_last_error(None).decode())
+    return agg, na.value
+
+
+def amg_transfer_mv8(ctx, rowptr, col, vals, ncols, m, In, Out, add=False):
+    """Out = Op In (add: Out += Op In) with the AMG transfer kernels; Op host CSR of rowptr.size - 1 rows and ncols
+    columns, In / Out device MultiVector<double,8> panels of ncols / rows rows (eig_amg_transfer_mv8)."""
+    rowptr = np.ascontiguousarray(rowptr, np.int64)
+    col = np.ascontiguousarray(col, np.int32)
+    vals = np.ascontiguousarray(vals, np.float64)
+    ctx.check(lib.eig_amg_transfer_mv8(ctx.h, int(add), rowptr.size - 1, ncols, _np_ptr(rowptr), _np_ptr(col),
+                                       _np_ptr(vals), m, In.ptr, Out.ptr))
 
 
 def permute_symmetric(rowptr, col, vals, perm):

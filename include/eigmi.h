@@ -715,6 +715,35 @@ int eig_mg_info(eig_mg_t mg, int *levels, int64_t *coarse_rows, int *coarse_degr
  * ||B - A X|| / ||B|| afterwards (a measurement; synchronous either way).  X must not alias B. */
 int eig_mg_solve(eig_mg_t mg, int64_t m, const double *B, double *X, int cycles, double *resid_host);
 int eig_mg_destroy(eig_mg_t mg);
+/* Algebraic multigrid (smoothed aggregation) for a square, single-rank, symmetric positive definite matrix with
+ * 1x1 blocks and no grid: any sparsity pattern (scrambled or reordered matrices, Matrix Market imports, matrices
+ * walked out of an unstructured grid).  The handle is an eig_mg_t: eig_mg_solve, eig_mg_info, eig_mg_destroy,
+ * eig_lobpcg_precond_mg and eig_blanczos_create_si_mg take it like a geometric one.
+ * Setup on the host, from the matrix alone, level l = 0, 1, ...: entry j != i of row i is strong when |a_ij| >=
+ * theta_l sqrt(a_ii a_jj), theta_l = theta / 2^l; rows are aggregated in three deterministic serial passes (a row
+ * whose strong neighbours are all free founds an aggregate with them; a remaining row joins its strongest
+ * aggregated strong neighbour's; the rest found aggregates with their free strong neighbours or stay singletons);
+ * P = (I - omega D^-1 A) T, T[i, agg(i)] = 1, omega = 4 / (3 lmax), lmax the Gershgorin bound of D^-1 A; A_c = P^T A P,
+ * bitwise symmetric.  A level of <= 256 rows is the coarsest (solved like the geometric one's); a level that
+ * coarsens by less than a factor 2 is the coarsest when it has <= 1024 rows, otherwise creation fails with
+ * EIG_ERR_ARG and the level sizes reached in the message (e.g. theta above a stencil's uniform strength, 1/6 for the
+ * 7-point one); at most 16 levels.  Smoothing, the V-cycle and the workspace are eig_mg_create's.
+ * Blocks other than 1x1: EIG_ERR_BLOCKSIZE.  A distributed context, a non-square matrix, theta < 0:
+ * EIG_ERR_ARG.  A non-positive diagonal entry on any level: EIG_ERR_BREAKDOWN. */
+int eig_amg_create(eig_mat_t A, double theta, int max_cols, int smooth_degree, double smooth_ratio, eig_mg_t *mg);
+/* One level of either kind of hierarchy (0 = the matrix itself): its scalar rows, stored scalar entries and the
+ * Gershgorin bound lmax of its D^-1 A; outputs or NULL.  Operator complexity = sum of nnz / nnz of level 0. */
+int eig_mg_level_info(eig_mg_t mg, int level, int64_t *rows, int64_t *nnz, double *lmax);
+/* The aggregation pass of eig_amg_create alone, host-only (no context): agg[i] in [0, *naggregates) for the n x n
+ * CSR matrix (ascending columns) at the threshold theta_l. */
+int eig_amg_aggregate(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, double theta_l,
+                      int64_t *agg, int64_t *naggregates);
+/* The hierarchy's transfer kernels on an operator given as host CSR (nrows x ncols, ascending columns; uploaded for
+ * the call), In and Out device MultiVector<double,8> panels of ncols and nrows rows, m in {8,16,24,32} columns:
+ * add = 0: Out = Op In (the restriction, Op = P^T); add != 0: Out += Op In (the prolongation, Op = P).  A row's
+ * stored entries are summed in turn; only the nrows rows of Out are written. */
+int eig_amg_transfer_mv8(eig_ctx_t ctx, int add, int64_t nrows, int64_t ncols, const int64_t *rowptr, const int32_t *col,
+                         const double *val, int64_t m, const double *In, double *Out);
 /* eig_blanczos_create_si with the Ks solve by `cycles` multigrid iterations (mg built on Ks with
  * max_cols >= block) instead of Chebyshev-Jacobi -- the smallest end of the pencil at 256^3, where
  * kappa(diag(K)^-1 K) ~ 2.7e4 would need ~2,500 Chebyshev steps per application. */

@@ -631,6 +631,16 @@ class Multigrid {
   {
     check(eig_mg_create(A.get(), nx, ny, nz, max_cols, smooth_degree, smooth_ratio, &h_), ctx_);
   }
+  // Smoothed-aggregation algebraic multigrid on a square single-rank SPD matrix with 1x1 blocks and any pattern
+  // (eig_amg_create): no grid; theta is the strength threshold of level 0, halved per level.
+  static Multigrid amg(const Matrix &A, double theta = 0.08, int max_cols = 32, int smooth_degree = 2,
+                       double smooth_ratio = 5.0)
+  {
+    eig_mg_t h = nullptr;
+    check(eig_amg_create(A.get(), theta, max_cols, smooth_degree, smooth_ratio, &h), A.ctx());
+    return Multigrid(A.ctx(), h);
+  }
+  Multigrid(Multigrid &&o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
   Multigrid(const Multigrid &) = delete;
   Multigrid &operator=(const Multigrid &) = delete;
   ~Multigrid() { eig_mg_destroy(h_); }
@@ -650,9 +660,21 @@ class Multigrid {
     check(eig_mg_solve(h_, (int64_t)B.cols(), B.data(), X.data(), cycles, want_resid ? &r : nullptr), ctx_);
     return r;
   }
+  // one level of either kind of hierarchy (0 = the matrix itself)
+  struct LevelInfo {
+    int64_t rows, nnz;
+    double lmax;
+  };
+  LevelInfo level_info(int level) const
+  {
+    LevelInfo i{};
+    check(eig_mg_level_info(h_, level, &i.rows, &i.nnz, &i.lmax), ctx_);
+    return i;
+  }
   eig_mg_t get() const { return h_; }
 
  private:
+  Multigrid(eig_ctx_t ctx, eig_mg_t h) : ctx_(ctx), h_(h) {}
   eig_ctx_t ctx_;
   eig_mg_t h_ = nullptr;
 };

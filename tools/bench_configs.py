@@ -21,6 +21,12 @@
       blocked residual and the point Chebyshev step beside the same run's blocked product (interleaved), and
       LOBPCG block 32 on the C3 pencil with one V-cycle against Chebyshev-Jacobi degree 4; mgblk_stats turns
       the kernel-trace summary of that run into one line per blocked kernel (block-Jacobi step, transfers)
+  AMG  smoothed-aggregation AMG on the bench's `general` matrix (3-D Poisson 128^3, scrambled + reverse
+      Cuthill-McKee, SELL with explicit columns): setup, levels and operator complexity, one V-cycle at m = 8 and
+      32 beside the geometric multigrid's on the unscrambled matrix in the same process (interleaved), the
+      residual per cycle, the transfers' algorithmic bytes, and LOBPCG block 32 with one AMG V-cycle against
+      Chebyshev-Jacobi degree 4; amg_stats turns a kernel trace of that run into one line per transfer kernel
+      and level
 
 One JSON line per measurement; algorithmic bytes per SURVEY 8(d); peak 8 TB/s.
 """
@@ -824,9 +830,110 @@ def mgblk_stats(path, m):
              min_us=round(min(t), 2), max_us=round(max(t), 2))
 
 
+def amg(ctx):
+    """Smoothed-aggregation AMG (eig_amg_create; theta 0.08, smoother degree 2, ratio 5) on the bench's `general`
+    matrix: 3-D Poisson EIGMI_AMG_N^3 (default 128), scrambled + reverse Cuthill-McKee.  Host setup + uploads;
+    levels, rows, stored entries, operator complexity; the fine-level transfers' algorithmic bytes (P's pattern
+    from eig_amg_aggregate: 12 nnz(P) + 8 (rows + 1) of CSR, the input panel once, the output panel once -- twice for
+    the prolongation, which adds in place); one V-cycle (eig_mg_solve, cycles = 1, synchronous) at the widths
+    EIGMI_AMG_M (default 8,32) interleaved over three rounds with the geometric multigrid's V-cycle on the
+    unscrambled matrix of the same size, and the residual after 1 and 8 cycles of both; LOBPCG block 32, nev 8,
+    tol 1e-8 with one AMG V-cycle and with Chebyshev-Jacobi degree 4 on [g / 10, g] (at most EIGMI_AMG_ITERS = 400
+    iterations each; 0 skips it).  The transfer kernels' own times come from a kernel trace of this config
+    (tools/gpu.sh amg, amg_stats below)."""
+    N = int(os.environ.get("EIGMI_AMG_N", "128"))
+    n = N ** 3
+    cfg = f"general 3-D Poisson {N}^3 (scrambled + RCM), smoothed-aggregation AMG"
+    rp0, c0, v0 = eigmi.gen_matrix(eigmi.GEN_POISSON3D, N)
+    t0 = time.perf_counter()
+    rp, c, v = eigmi.scrambled_rcm(rp0, c0, v0)
+    t_perm = time.perf_counter() - t0
+    K = eigmi.Matrix.from_bcsr(ctx, rp, c, v)
+    theta, nu, ratio = 0.08, 2, 5.0
+    t0 = time.perf_counter()
+    mg = eigmi.Multigrid.amg(K, theta, max_cols=32, smooth_degree=nu, smooth_ratio=ratio)
+    setup_s = time.perf_counter() - t0
+    lev = [mg.level_info(l) for l in range(mg.info()["levels"])]
+    emit(config=cfg, op="hierarchy setup (host aggregation, P, P^T A P, uploads)", s=round(setup_s, 2),
+         scramble_rcm_s=round(t_perm, 2), spmm32_kernel=K.kernel("spmm32"), theta=theta, smooth_degree=nu,
+         smooth_ratio=ratio, rows=[L["rows"] for L in lev], nnz=[L["nnz"] for L in lev],
+         operator_complexity=round(mg.complexity(), 4), mg=mg.info())
+    agg, na = eigmi.amg_aggregate(rp, c, v, theta)
+    row = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+    nnz_p = int(np.unique(row * na + agg[c]).size)  # P's pattern: the aggregates of a row's stored columns
+    Kg = eigmi.Matrix.from_bcsr(ctx, rp0, c0, v0)
+    t0 = time.perf_counter()
+    geo = eigmi.Multigrid(Kg, (N, N, N), max_cols=32, smooth_degree=nu, smooth_ratio=ratio)
+    emit(config=cfg, op="geometric multigrid on the unscrambled matrix: setup", s=round(time.perf_counter() - t0, 2),
+         spmm32_kernel=Kg.kernel("spmm32"), mg=geo.info(),
+         rows=[geo.level_info(l)["rows"] for l in range(geo.info()["levels"])])
+    for m in [int(x) for x in os.environ.get("EIGMI_AMG_M", "8,32").split(",")]:
+        B, X = ctx.array(oracle.random_mv8(n, m, 2)), ctx.zeros(n * m)
+        res = {}
+        for name, h in (("amg", mg), ("geometric", geo)):
+            r1 = h.solve(m, B, X, 1, resid=True)
+            r8 = h.solve(m, B, X, 8, resid=True)
+            res[name] = (r1, r8, (r8 / r1) ** (1.0 / 7.0))
+        rounds = {"amg": [], "geometric": []}
+        for _ in range(3):
+            for name, h in (("amg", mg), ("geometric", geo)):
+                rounds[name].append(wall(lambda: h.solve(m, B, X, 1), 10)[0] * 1e3)
+        restrict_b = 12 * nnz_p + 8 * (na + 1) + 8 * m * (n + na)
+        prolong_b = 12 * nnz_p + 8 * (n + 1) + 8 * m * (2 * n + na)
+        emit(config=cfg, op=f"one V-cycle m={m} (eig_mg_solve, cycles = 1, synchronous; interleaved, 3 rounds of 10)",
+             amg_ms=[round(x, 3) for x in rounds["amg"]], geometric_ms=[round(x, 3) for x in rounds["geometric"]],
+             amg_min_ms=round(min(rounds["amg"]), 3), geometric_min_ms=round(min(rounds["geometric"]), 3),
+             amg_residual_after_1=res["amg"][0], amg_residual_after_8=res["amg"][1],
+             amg_contraction_per_cycle=round(res["amg"][2], 4), geometric_residual_after_1=res["geometric"][0],
+             geometric_residual_after_8=res["geometric"][1], geometric_contraction_per_cycle=round(res["geometric"][2], 4),
+             fine_aggregates=int(na), nnz_P=nnz_p, restrict_algorithmic_bytes=restrict_b,
+             prolong_algorithmic_bytes=prolong_b)
+        B.free(), X.free()
+    geo.close()
+    Kg.close()
+    g = float((np.add.reduceat(np.abs(v), rp[:-1]) / v[c == row]).max())
+    b, nev, tol, cap = 32, 8, 1e-8, int(os.environ.get("EIGMI_AMG_ITERS", "400"))
+    for name in ("one AMG V-cycle", "Chebyshev-Jacobi degree 4") if cap > 0 else ():
+        s = eigmi.Lobpcg(K, None, block=b, seed=123)
+        if name == "one AMG V-cycle":
+            s.precond_mg(mg, 1)
+        else:
+            s.precond_cheb(4, g / 10.0, g)
+        tw, (it, conv, t) = wall(lambda: s.step(cap, nev, tol))
+        ev, _, rs = s.ritz(nev)
+        emit(config=cfg + f", LOBPCG block {b}, nev {nev}, tol {tol:g}", op=name, iterations=it, converged=conv,
+             device_ms=round(t.total_ms, 1), ms_per_iteration=round(t.total_ms / max(it, 1), 2),
+             precond_ms_per_iteration=round(t.precond_ms / max(it, 1), 2), wall_s=round(tw, 2),
+             eigenvalues=[float(x) for x in ev], relative_residuals=[float(a / abs(e)) for a, e in zip(rs, ev)])
+        s.close()
+    mg.close()
+    K.close()
+
+
+def amg_stats(path, m):
+    """The transfer kernels of both hierarchies in a rocprofv3 --kernel-trace of amg at one width m: per kernel and
+    grid size (one per level, the largest first) the dispatches, their median and minimum."""
+    import csv
+    keys = ("k_amg_restrict", "k_amg_prolong_add", "k_mg_restrict", "k_mg_prolong_add")
+    runs = {}
+    for r in csv.DictReader(open(path)):
+        name = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("eigmi::", "")
+        if any(k in name for k in keys):
+            grid = int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"])
+            runs.setdefault(name, {}).setdefault(grid, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for name, by_grid in sorted(runs.items()):
+        for level, grid in enumerate(sorted(by_grid, reverse=True)):
+            t = by_grid[grid]
+            emit(m=int(m), kernel=name, level=level, grid_threads=grid, calls=len(t),
+                 median_us=round(float(np.median(t)), 2), min_us=round(min(t), 2), max_us=round(max(t), 2))
+
+
 if __name__ == "__main__":
     if sys.argv[1:2] == ["mgblk_stats"]:
         mgblk_stats(sys.argv[2], sys.argv[3])
+        sys.exit(0)
+    if sys.argv[1:2] == ["amg_stats"]:
+        amg_stats(sys.argv[2], sys.argv[3])
         sys.exit(0)
     ctx = eigmi.Context(0)
     which = sys.argv[1:] or ["c1", "c2", "c3", "inv"]

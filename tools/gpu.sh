@@ -23,6 +23,8 @@
 #                        c5si in one process; the same under a kernel trace   -> lobpcg.jsonl, lobpcg_trace/
 #   mgblk                the blocked multigrid at C3 size (q1elast 64^3, 3x3): V-cycle, residual / Chebyshev A/B, LOBPCG
 #                        with one V-cycle vs Chebyshev degree 4; then the same under a kernel trace -> mgblk.jsonl, mgblk_kernels.jsonl
+#   amg                  smoothed-aggregation AMG on the general (scrambled + RCM) Poisson 128^3: setup, V-cycle beside the
+#                        geometric one, LOBPCG vs Chebyshev degree 4; then a kernel trace per width -> amg.jsonl, amg_kernels.jsonl
 #   latency              fused step vs eig_mv across sizes and slabs, plane-run counts  -> latency.jsonl
 #   marchcopy            the march streams alone (tools/march_copy.hip)       -> march_copy.jsonl
 #   prefetch             geometric march prefetch variants x plane runs (256^3, 128^3, slab) -> latency.jsonl
@@ -137,6 +139,17 @@ run_task() {
         EIGMI_MGBLK_M=$m EIGMI_MGBLK_ITERS=0 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$O/mgblk_trace$m" -o trace -- \
           python3 tools/bench_configs.py mgblk > "$O/mgblkt$m.jsonl" 2> "$O/mgblkt$m.err" || return 1
         python3 tools/bench_configs.py mgblk_stats "$(find "$O/mgblk_trace$m" -name '*kernel_trace.csv' | head -1)" $m >> "$O/mgblk_kernels.jsonl" || return 1
+      done ;;
+    amg)
+      # plain run for the wall-clock numbers, then a kernel trace per width for the transfer kernels' own times
+      # (k_amg_restrict / k_amg_prolong_add beside k_mg_restrict / k_mg_prolong_add in one process)
+      prof_env
+      timeout -k 10 500 python -u tools/bench_configs.py amg > "$O/amg.jsonl" 2> "$O/amg.err" || return 1
+      : > "$O/amg_kernels.jsonl"
+      for m in 8 32; do
+        EIGMI_AMG_M=$m EIGMI_AMG_ITERS=0 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$O/amg_trace$m" -o trace -- \
+          python3 tools/bench_configs.py amg > "$O/amgt$m.jsonl" 2> "$O/amgt$m.err" || return 1
+        python3 tools/bench_configs.py amg_stats "$(find "$O/amg_trace$m" -name '*kernel_trace.csv' | head -1)" $m >> "$O/amg_kernels.jsonl" || return 1
       done ;;
     lobpcgtrace)
       # the same under a kernel trace: k_lobpcg_update / k_lobpcg_resid and the rest of an iteration per kernel
