@@ -373,7 +373,7 @@ void halo_split(eig_mat_s &A, hipEvent_t e0, hipEvent_t e1, Halo halo, Launch la
   }
   if (march_split_active(A))
   {
-    // interior planes on the plane march (k_spmv.hip), every other slice after the exchange
+    // interior planes on the plane march (k_march.hip), every other slice after the exchange
     const bool has_bd = A.n_march_bnd > 0;
     launch(&kMarchInteriorTag, 0, 0, has_bd ? kPartFirst : kPartOnly);
     if (!ctx->loop) EIG_HIP(hipStreamWaitEvent(s, e1, 0));
@@ -416,7 +416,7 @@ void lanczos_step(eig_mat_s &A, double *u, double *up, double *t, int j, Lanczos
   mark(4);
 }
 
-// One fused launch L (k_spmv.hip "Fused one-reduction Lanczos step"; a step or a repair, decided
+// One fused launch L (spmv_dev.h "Fused one-reduction Lanczos step"; a step or a repair, decided
 // on the device): P = interleaved pairs of the previous launch (window layout, ghosts exchanged
 // here), the output pairs go to Pout; one allreduce of the launch's three sums.  Events as
 // lanczos_step: ev[0] before, ev[1] after the kernel, ev[2..4] after the allreduce.

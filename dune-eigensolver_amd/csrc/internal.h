@@ -264,18 +264,18 @@ struct eig_mat_s {
   // planes): the rows form an nx x ny x nz grid (offsets -D, -nx, -1, 0, 1, nx, D with D = nx ny, or
   // the 2-D -D, -1, 0, 1, D with D = nx) and every row stores exactly its in-grid neighbours; the
   // march derives the masks from the coordinates (uniform bands: values from the arguments; other
-  // bands: the value march streams the band arrays, k_spmv.hip march variant 10)
+  // bands: the value march streams the band arrays, k_march.hip march variant 10)
   bool sym_geo = false;
   int sym_gx = 0, sym_gy = 0, sym_gz = 0, sym_gz0 = 0;  // grid (global planes) and this rank's first plane
   // Box-geometric masks (mat_image.cpp build_sym_image): offsets inside the 27-point box a D + b nx + c (a, b, c in
   // {-1, 0, 1}) of an nx x ny x nz grid, every row storing exactly its in-grid neighbours among them
   // (sym_geo's 5 / 7-point grids excluded); sym_box27 = bit (a + 1) 9 + (b + 1) 3 + (c + 1) per stored
-  // offset; grid in sym_gx / gy / gz / gz0.  The box marches (k_spmv.hip, e.g. the P1 Kuhn 15-point
+  // offset; grid in sym_gx / gy / gz / gz0.  The box marches (k_march.hip, e.g. the P1 Kuhn 15-point
   // stencil of config C5) derive the masks from the coordinates
   unsigned sym_box27 = 0;
   // packed copy of the 4 value arrays of a 7-point band ({+D, 0, +1, +nx} per row, 32 B; the P1 Kuhn
   // band: 8 arrays, 64 B) for the march variants whose values are kMarchPack (march_variants.h;
-  // k_spmv.hip sym_pack_prepare: built at the first launch that marches on it, never by a query;
+  // k_march.hip sym_pack_prepare: built at the first launch that marches on it, never by a query;
   // refilled in place by a shift)
   double *sym_pack = nullptr;
   eigmi::i64 sym_pack_bytes = 0;
@@ -349,7 +349,7 @@ struct LanczosState {
   double *nsum;   // nsum[j]  = ||u_j||^2 (local, then allreduced); nsum[0] from the start vector
   double *alpha;  // alpha[j]
   double *beta;   // beta[j]  = sqrt(nsum[j])
-  // fused step (k_spmv.hip "Fused one-reduction Lanczos step"), indexed by LAUNCH L (a repair is a
+  // fused step (spmv_dev.h "Fused one-reduction Lanczos step"), indexed by LAUNCH L (a repair is a
   // launch that is not a step):
   double *fred;   // fred[3L..3L+2] = (t . u, t . t, u . u) of launch L (local, then allreduced)
   int *ctl;       // ctl[2L], ctl[2L+1] = logical step and mode at the start of launch L
@@ -377,7 +377,7 @@ void launch_lanczos_pipe(const eig_mat_s &A, double *T, double *UZ, const double
                          double *out, hipStream_t s, ReduceWS red);
 // beta / nsum of the current logical step after a repair launch (L = the next launch index)
 void launch_fused_tail(const LanczosState &st, int L, hipStream_t s);
-// Plane march (kernels and launchers: k_spmv.hip; selection, plans and queries: march_plan.h / march_plan.cpp):
+// Plane march (kernels and launchers: k_march.hip; selection, plans and queries: march_plan.h / march_plan.cpp):
 // band geometry (widest offset D) and whether the interior-plane split
 // launch applies now (split built at upload, image and EIGMI_* switches allow it).  Passing
 // slices == &kMarchInteriorTag to launch_spmv / launch_lanczos_spmv / launch_lanczos_fused marches
@@ -387,6 +387,17 @@ bool march_split_active(const eig_mat_s &A);
 int march_variant(const eig_mat_s &A, bool fused);
 int march_pipe(const eig_mat_s &A);  // 1: a whole-matrix fused launch takes the pipelined 2-line body
 extern const i32 kMarchInteriorTag;
+// The march half of those three launchers (k_march.hip), mode = image_mode(A): true when a march kernel was
+// launched, false (nothing launched) when no plan applies and the slice kernels are to run.
+struct FusedArgs;  // (spmv_dev.h: the fused step's scalars as a kernel argument)
+bool launch_spmv_march(const eig_mat_s &A, int mode, const double *x, double *y, const i32 *slices, i64 first,
+                       i64 count, hipStream_t s, bool keep);
+bool launch_lanczos_spmv_march(const eig_mat_s &A, int mode, const double *u, const double *up, double *t, int j,
+                               const LanczosState &st, const i32 *slices, i64 first, i64 count, double *dot_out,
+                               double *beta_out, int ticket, hipStream_t s, ReduceWS red);
+bool launch_lanczos_fused_march(const eig_mat_s &A, int mode, const double *P, double *Pout, const FusedArgs &fa,
+                                int L, const i32 *slices, i64 first, i64 count, double *out, int ticket,
+                                hipStream_t s, ReduceWS red);
 // a2 SpMM (kernels_cpp.hh:626-657) on the band-image plane march for 1x1 matrices whose band
 // qualifies; false (nothing launched) otherwise.  X, Y: window-layout multivectors, m % 8 == 0.
 bool box_prepare(const eig_mat_s &A);
@@ -477,7 +488,7 @@ void launch_stream_copy(i64 n, const double *x, double *y, int num_cu, hipStream
 void launch_scal_dev(i64 n, const double *a, bool reciprocal_sqrt, double *x, hipStream_t s);
 void launch_sqrt_inplace(double *v, int count, hipStream_t s);
 void launch_shift_diag(eig_mat_s &A, double shift, hipStream_t s);
-// (Re)fill the packed value image sym_pack from the band arrays on stream s (k_spmv.hip)
+// (Re)fill the packed value image sym_pack from the band arrays on stream s (k_march.hip)
 void sym_pack_fill(eig_mat_s &A, hipStream_t s);
 
 // MultiVector<double,8> kernels.

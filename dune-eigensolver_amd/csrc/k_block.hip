@@ -428,7 +428,7 @@ int sell_mv8_launches(i64 m)
 
 void launch_sell_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, hipStream_t s)
 {
-  // symmetric band image with a marchable band (3-D / 2-D stencils): k_spmm8_march (k_spmv.hip)
+  // symmetric band image with a marchable band (3-D / 2-D stencils): k_spmm8_march (k_march.hip)
   // 3-D box stencils (7-point, P1 Kuhn), 32 columns per matrix pass: LDS-tiled plane march (k_box.hip)
   if (launch_box_spmm(A, m, X, Y, s)) return;
   if (launch_spmm_march(A, m, X, Y, s)) return;

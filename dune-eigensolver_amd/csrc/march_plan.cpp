@@ -1,4 +1,4 @@
-// march_plan.cpp -- host side of the plane march (kernels: k_spmv.hip): does an image march, which variant
+// march_plan.cpp -- host side of the plane march (kernels: k_march.hip): does an image march, which variant
 // (march_variants.h) runs, with how many plane runs, in which direction, with which body and cache policy;
 // the byte model and the kernel-name queries.  Plain C++: every function reads a matrix's host-side fields
 // (and its context's num_cu / distributed()) and nothing else -- no allocation, no launch, no device access --
@@ -157,7 +157,7 @@ bool march_geometry(const eig_mat_s &A, i64 &D, int chunk)
 // [zb, ze): plane range of a split launch (the interior planes of a distributed slab); ze < 0 =
 // the whole matrix.
 // chunk: rows per wave column (64 for the scalar kernels, 16 for the 8-column SpMM).
-// MarchPlan::pack stays null: the launch paths (k_spmv.hip launch_plan, march_prepare) build the value pack
+// MarchPlan::pack stays null: the launch paths (k_march.hip launch_plan, march_prepare) build the value pack
 // the plan's variant streams and set it; a query leaves it unbuilt.
 MarchPlan march_plan(const eig_mat_s &A, int mode, i64 zb, i64 ze, bool fused, int chunk)
 {
@@ -252,7 +252,7 @@ MarchPlan march_plan(const eig_mat_s &A, int mode, i64 zb, i64 ze, bool fused, i
   mp.tstore = fused && T.geo2_path() && (vectors_fit_mall(A) || (A.tune_cache & 1));
   mp.cache = A.tune_cache;
   // EIG_TUNE_CACHE 16: every launch of the 2-line variants with a downward body marches down (eig_mv and the
-  // classic K1 too, when tuned onto them).  The fused step's alternation (neither bit, or both): launch_lanczos_fused
+  // classic K1 too, when tuned onto them).  The fused step's alternation (neither bit, or both): launch_lanczos_fused_march
   mp.down = T.down_body && (A.tune_cache & 24) == 16;
   // the pipelined body (march_rows_geo2_2l<DOWN, PIPE>) takes kMarchPipeLds of LDS per workgroup -- one
   // workgroup per CU -- so it is on only where the launch has no more than that anyway: the two-run plan on

@@ -1,4 +1,4 @@
-// march_plan.h -- what the plane-march kernels (k_spmv.hip) and their host-side planning (march_plan.cpp)
+// march_plan.h -- what the plane-march kernels (k_march.hip) and their host-side planning (march_plan.cpp)
 // share: the image modes, the plan structures passed as kernel arguments, and the selection / planning /
 // query functions.  Host-only declarations and plain data: no device code, so host tests compile
 // march_plan.cpp with this header and no GPU.
@@ -18,7 +18,7 @@ constexpr int kWaves = kStreamThreads / 64;
 // the same with the lane-shift path for the offsets -1 / 0 / +1.
 enum { kExplicit = 0, kStencil = 1, kMixed = 2, kSym8 = 3, kSym32 = 4, kSymN8 = 5, kSymN32 = 6 };
 
-// Plan of one plane-march launch (march_plan; a kernel argument of the march kernels of k_spmv.hip, whose
+// Plan of one plane-march launch (march_plan; a kernel argument of the march kernels of k_march.hip, whose
 // "Plane-marching fused step" comment describes the march itself).
 struct MarchPlan {
   i64 D;        // rows per plane (the band's widest offset)
@@ -63,12 +63,12 @@ struct MarchPlan {
   int pipe;
 };
 
-// The pipelined body's LDS (k_spmv.hip "PIPE"): two buffers per wave of kMarchPipeRegions lane-linear regions
+// The pipelined body's LDS (k_march.hip "PIPE"): two buffers per wave of kMarchPipeRegions lane-linear regions
 // of 64 x 16 B, one region per load of a plane.
 constexpr int kMarchPipeRegions = 13;
 constexpr unsigned kMarchPipeBuf = kMarchPipeRegions * 1024u;  // one plane of one wave
 constexpr unsigned kMarchPipeLds = kWaves * 2 * kMarchPipeBuf;  // dynamic LDS of a pipelined launch
-constexpr int kMaxPipeDevices = 64;  // device indices whose kernels launch_lanczos_fused has raised to it
+constexpr int kMaxPipeDevices = 64;  // device indices whose kernels launch_lanczos_fused_march has raised to it
 
 // General band march (k_spmm8_marchg): the gathered offsets of a span, and the spans of an image (gspans).
 constexpr int kGSpan = 3;
@@ -77,7 +77,7 @@ struct GSpans {
   int s1b, s1e, s2b, s2e, s3b, s3e, s4b, s4e;
 };
 
-// The 2-line fused march (variant 22; k_spmv.hip march_rows_geo2_2l)
+// The 2-line fused march (variant 22; k_march.hip march_rows_geo2_2l)
 // is the default on ranks of at least EIG_MARCH_2L_MIN_ROWS rows: 256^3 (16.8 M
 // rows) 206.5-206.8 us vs 223.5 us for variant 15 (profiles/r06e_sweep256_2lines.jsonl, 0.65 of HBM),
 // but 2 M-row grids (128^3, one rank's 256^2 x 32 slab) 28.2-28.4 vs 27.7-27.9 us: fewer, longer
@@ -86,8 +86,8 @@ struct GSpans {
 // per column on wide planes (march_plan, round 6) 4 M rows 45.6 vs 46.0 us, 2 M rows 27.6 either way --
 // the threshold is 4 M.
 constexpr bool kMarch2lDefault = true;
-// Serpentine (the downward body: k_spmv.hip "DOWN", MarchTraits::down_body):
-// A fused launch of variant 22 / 23 marches down when its launch index is odd (launch_lanczos_fused).
+// Serpentine (the downward body: k_march.hip "DOWN", MarchTraits::down_body):
+// A fused launch of variant 22 / 23 marches down when its launch index is odd (launch_lanczos_fused_march).
 // Measured at 256^3, one process, 7 interleaved rounds (profiles/r07_serpentine_ab.jsonl): every
 // launch upward 191.8 us (max - min over rounds 1.0), every launch downward 198.4 us (the downward body is
 // the slower one), alternating 185.0 us -- each launch gains what the memory-side cache still holds of the
@@ -110,7 +110,7 @@ int march_launch_variant(const eig_mat_s &A, int mode, int variant);
 unsigned march_grid(const MarchPlan &mp);  // workgroups of the plan's launch
 int box_band_array(const eig_mat_s &A, i64 D, int q);
 // The plan of a launch on planes [zb, ze) (ze < 0: the whole matrix), nseg = 0 where nothing marches.
-// MarchPlan::pack stays null: a launch sets it (k_spmv.hip launch_plan), a query has no use for it.
+// MarchPlan::pack stays null: a launch sets it (k_march.hip launch_plan), a query has no use for it.
 MarchPlan march_plan(const eig_mat_s &A, int mode, i64 zb = 0, i64 ze = -1, bool fused = false, int chunk = 64);
 // Whether a whole-matrix launch on A marches (one rank, or no halo: the whole plan; else the interior-plane
 // split).  Tests the eig_mv / K1 plan, also where the caller goes on to name the fused kernel.

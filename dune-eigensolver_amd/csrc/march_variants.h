@@ -1,5 +1,5 @@
-// The plane-march variants (k_spmv.hip): what each variant number IS, in one table.  The kernels'
-// `if constexpr`s and __launch_bounds__ and the launch dispatch (k_spmv.hip), the selection (march_select),
+// The plane-march variants (k_march.hip): what each variant number IS, in one table.  The kernels'
+// `if constexpr`s and __launch_bounds__ and the launch dispatch (k_march.hip), the selection (march_select),
 // the run-count, direction and body rules of march_plan and the byte model of lanczos_kernel_info
 // (march_plan.cpp) all read it; adding or retiring a variant is one row here plus its entry in MarchDispatch.  The numbers are public
 // (eig_mat_info.march_variant, the profiler's kernel instance names) and do not change.
@@ -10,7 +10,7 @@
 
 namespace eigmi {
 
-// Row-loop body a variant runs (templates of k_spmv.hip).
+// Row-loop body a variant runs (templates of k_march.hip).
 enum MarchFamily {
   kMarchMasked,  // march_rows' own body: masked selects, any band the march takes
   kMarchGeo,     // march_rows_geo<PF, PG>: whole planes, masks from the coordinates

@@ -69,7 +69,7 @@ static void block_lanczos(eig_ctx_t ctx, int N, int64_t b, int64_t cnt, bool dis
   eig_mat_destroy(M);
 }
 
-// Guarded fused step with repairs (k_spmv.hip fused_begin): Poisson plus +100 on the diagonal of
+// Guarded fused step with repairs (spmv_dev.h fused_begin): Poisson plus +100 on the diagonal of
 // 12 rows puts trace/n away from the bulk, so some launches repair instead of stepping; the
 // repair and the step after it run through the interior / boundary split with the carry.
 static const int kRsteps = 14;
@@ -91,7 +91,7 @@ static void fused_repair_run(eig_mat_t A, double *a, double *be, int *launches, 
   CK(eig_lanczos_destroy(ws));
 }
 
-// Value-streaming images (k_spmv.hip march variant 15 where the grid allows) and the uniform-
+// Value-streaming images (k_march.hip march variant 15 where the grid allows) and the uniform-
 // band check across rank interfaces: (a) the variable-coefficient 7-point matrix (eig_gen kind 8);
 // (b) the Poisson matrix whose z couplings across plane pz (rows of planes pz - 1 / pz, both mirror
 // entries) are -2: every rank's own upper entries are still one constant per diagonal, but the

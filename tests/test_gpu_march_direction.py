@@ -1,4 +1,4 @@
-"""Direction of the 2-line value march (k_spmv.hip march_rows_geo2_2l<DOWN>, march variants 22 / 23,
+"""Direction of the 2-line value march (k_march.hip march_rows_geo2_2l<DOWN>, march variants 22 / 23,
 MarchPlan::down; DESIGN.md 4e "serpentine"): a launch may march its plane runs from the last plane down
 to the first, so that it starts on the planes the launch before it touched last.
 

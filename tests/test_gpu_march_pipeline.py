@@ -1,4 +1,4 @@
-"""Pipelined body of the fused 2-line value march (k_spmv.hip march_rows_geo2_2l<DOWN, PIPE>, MarchPlan::pipe;
+"""Pipelined body of the fused 2-line value march (k_march.hip march_rows_geo2_2l<DOWN, PIPE>, MarchPlan::pipe;
 DESIGN.md 4e "pipeline"): every loop load of variants 22 / 23 goes through LDS as an LDS-DMA issued one plane
 ahead.  The body does the plain body's arithmetic in its order and a lane adds its rows into the launch's
 three sums in the same order, so against the plain body of the SAME build (EIG_TUNE_CACHE 32 = never

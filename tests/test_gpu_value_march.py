@@ -1,4 +1,4 @@
-"""The value-streaming plane march (k_spmv.hip march_rows_geo2<VAL>, march variants 10 / 11): the
+"""The value-streaming plane march (k_march.hip march_rows_geo2<VAL>, march variants 10 / 11): the
 BCRSMatrix::mv / Lanczos step kernels on a geometric 7-point (or 5-point) band whose values are NOT
 constant, so every stored value is read from the symmetric band arrays in HBM on every launch
 (the reference reads every stored value per call: kernels_cpp.hh:611-617, arpack_geneo_wrapper.hh:275).
