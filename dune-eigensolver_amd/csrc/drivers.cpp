@@ -355,7 +355,7 @@ void halo_split(eig_mat_s &A, hipEvent_t e0, hipEvent_t e1, Halo halo, Launch la
     launch(nullptr, 0, A.nslices, kPartOnly);
     return;
   }
-  if (ctx->loop)
+  if (ctx->loopback())
     halo(s);
   else
   {
@@ -367,7 +367,7 @@ void halo_split(eig_mat_s &A, hipEvent_t e0, hipEvent_t e1, Halo halo, Launch la
   if (A.tune_halo_whole)
   {
     // EIG_TUNE_HALO = 1: wait for the exchange, then one launch over every owned row
-    if (!ctx->loop) EIG_HIP(hipStreamWaitEvent(s, e1, 0));
+    if (!ctx->loopback()) EIG_HIP(hipStreamWaitEvent(s, e1, 0));
     launch(nullptr, 0, A.nslices, kPartOnly);
     return;
   }
@@ -376,13 +376,13 @@ void halo_split(eig_mat_s &A, hipEvent_t e0, hipEvent_t e1, Halo halo, Launch la
     // interior planes on the plane march (k_march.hip), every other slice after the exchange
     const bool has_bd = A.n_march_bnd > 0;
     launch(&kMarchInteriorTag, 0, 0, has_bd ? kPartFirst : kPartOnly);
-    if (!ctx->loop) EIG_HIP(hipStreamWaitEvent(s, e1, 0));
+    if (!ctx->loopback()) EIG_HIP(hipStreamWaitEvent(s, e1, 0));
     if (has_bd) launch(A.march_bnd, 0, A.n_march_bnd, kPartSecond);
     return;
   }
   const bool has_in = A.n_interior > 0, has_bd = A.n_boundary > 0;
   if (has_in) launch(A.slice_list, 0, A.n_interior, has_bd ? kPartFirst : kPartOnly);
-  if (!ctx->loop) EIG_HIP(hipStreamWaitEvent(s, e1, 0));
+  if (!ctx->loopback()) EIG_HIP(hipStreamWaitEvent(s, e1, 0));
   if (has_bd) launch(A.slice_list, A.n_interior, A.n_boundary, has_in ? kPartSecond : kPartOnly);
 }
 
@@ -846,7 +846,7 @@ extern "C" int eig_lanczos_capture(eig_lanczos_t ws, int steps, int flags, int *
     ws->g_ev = make_events(steps, events_per_step(flags));
     if (captured) *captured = 0;
     // the loopback transport synchronises with the host inside the step: eager replay only
-    if (ctx->loop) return;
+    if (ctx->loopback()) return;
     hipStream_t s = ctx->stream;
     march_prepare(*ws->A);  // (builds a value pack outside the graph, never as a captured node)
     EIG_HIP(hipStreamSynchronize(s));

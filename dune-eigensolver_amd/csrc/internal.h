@@ -1,12 +1,9 @@
 // internal.h -- shared host-side structures of libeigmi (not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <complex>
-#include <condition_variable>
 #include <cstdint>
-#include <mutex>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -35,13 +32,6 @@ struct Error : std::runtime_error {
       throw ::eigmi::Error(EIG_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));     \
   } while (0)
 
-#define EIG_NCCL(call)                                                                         \
-  do {                                                                                         \
-    ncclResult_t r_ = (call);                                                                  \
-    if (r_ != ncclSuccess)                                                                     \
-      throw ::eigmi::Error(EIG_ERR_RCCL, std::string(#call) + ": " + ncclGetErrorString(r_));  \
-  } while (0)
-
 #define EIG_CHECK(cond, code, msg)                                                             \
   do {                                                                                         \
     if (!(cond)) throw ::eigmi::Error((code), (msg));                                          \
@@ -67,95 +57,9 @@ struct ReduceWS {
   unsigned *ticket(int t) const { return tickets + (size_t)t * kTicketStride; }
 };
 
-// In-process loopback transport: P virtual ranks (one host thread + context each, usually on the
-// same device) exchange through this hub instead of RCCL.  Test-only path for the distributed
-// code on a single GPU; every operation is synchronous.
-struct LoopHub {
-  int P = 1;
-  std::mutex m;
-  std::condition_variable cv;
-  int arrived = 0;
-  unsigned long gen = 0;
-  std::vector<double *> xptr;      // per rank: vector being exchanged
-  std::vector<i64> win_begin;      // per rank: window begin (scalar)
-  std::vector<std::vector<double>> red;
-  std::vector<i64> gather;
-  std::vector<u64 *> mbox;                 // per rank: its mailbox (eig_comm_loopback_mailbox)
-  std::vector<int> flag;                   // per rank: a flag agreed through the hub
-  void barrier()
-  {
-    std::unique_lock<std::mutex> lk(m);
-    const unsigned long g = gen;
-    if (++arrived == P)
-    {
-      arrived = 0;
-      ++gen;
-      cv.notify_all();
-    }
-    else
-      cv.wait(lk, [&] { return gen != g; });
-  }
-};
-
-// xGMI mailbox allreduce (k_comm.hip): each rank's uncached mailbox, IPC-mapped by every peer.
-constexpr int kMaxMailboxRanks = 16;
-constexpr int kMailboxVals = 63;  // values per call (slot = 1 sequence word + 63 values = 512 B)
-constexpr int kXchWords = 4;       // step region slot (xch_dev.h): sequence number + 3 sums
-struct Mailbox {
-  u64 *local = nullptr;                  // my mailbox: [2][P][1 + kMailboxVals], then the step region
-  u64 *peer[kMaxMailboxRanks] = {};      // peer[r] = rank r's mailbox mapped here (peer[me] = local)
-  u64 *ctr = nullptr;                    // device: sequence number of the last completed call
-  u64 *fctr = nullptr;                   // device: sequence number of the last fused-step exchange
-  int *err = nullptr;                    // device: set when a call timed out
-  long long foff = 0;                    // word offset of the step region [2][P][kXchWords] (xch_dev.h)
-  int P = 1, me = 0;
-};
-// Host-side ownership of the mailbox resources of a context.
-struct MailboxHost {
-  Mailbox dev;
-  u64 *local = nullptr;          // hipExtMallocWithFlags allocation (exported)
-  size_t bytes = 0;              // its size
-  void *state = nullptr;         // ctr + fctr + err (hipMalloc, 256 B)
-  std::vector<void *> opened;    // IPC-opened peer mappings (closed on destroy)
-  bool ready = false;            // peers opened and validated: allreduce_sum uses it
-  bool on = true;                // eig_comm_select_allreduce: false = ncclAllReduce although ready
-  bool step = false;             // EIG_AR_MAILBOX_STEP: the fused step exchanges its sums in-kernel
-};
-constexpr unsigned long long kMailboxTimeout = 1000000000ull;  // 10 s of s_memrealtime (100 MHz)
-void launch_mailbox_allreduce(double *buf, int count, const Mailbox &mb, unsigned long long timeout, hipStream_t s);
-
-// xGMI halo mailbox (k_comm.hip) of mailbox-only ranks (eig_comm_ipc_open, no RCCL): every rank's
-// uncached staging area, IPC-mapped by every peer.  Layout: [2][P] sequence lines (one 128-B line
-// per word), then [2][P][cap] doubles; parity = sequence & 1, slot = the sending rank.
-constexpr int kHaloFlagStride = 16;  // u64 words per sequence line
-struct HaloBox {
-  u64 *flags = nullptr;                         // mine: [2][P] lines
-  u64 *peer_flags[kMaxMailboxRanks] = {};       // rank r's lines mapped here (peer_flags[me] = flags)
-  double *stage = nullptr;                      // mine: [2][P][cap]
-  double *peer_stage[kMaxMailboxRanks] = {};
-  u64 *seq = nullptr;                           // device: [P] exchanges completed with each peer
-  unsigned *ticket = nullptr;                   // device: push / pull last-workgroup tickets (128 B apart)
-  int *err = nullptr;                           // the mailbox's error word (Mailbox::err)
-  long long cap = 0;                            // doubles per slot
-  int P = 1, me = 0;
-};
-struct HaloBoxHost {
-  HaloBox dev;
-  void *alloc = nullptr;         // hipExtMallocWithFlags allocation (exported)
-  void *state = nullptr;         // seq + tickets (hipMalloc, 512 B)
-  std::vector<void *> opened;    // IPC-opened peer mappings
-};
-// One side of an exchange: n ranges (peer, window offset, count) in scalar units.
-struct HaloXfer {
-  int n = 0;
-  int peer[kMaxMailboxRanks] = {};
-  long long off[kMaxMailboxRanks] = {};
-  long long cnt[kMaxMailboxRanks] = {};
-};
-void launch_halo_mailbox(const HaloBox &hb, const HaloXfer &snd, const HaloXfer &rcv, const HaloXfer &sync, double *x,
-                         double *x2, int width, hipStream_t s);
-
 }  // namespace eigmi
+
+#include "comm.h"  // the transport structures of eig_ctx_s and what comm.cpp offers
 
 struct eig_mg_s;  // mg.cpp
 
@@ -180,11 +84,16 @@ struct eig_ctx_s {
   long long n_ar = 0, n_ar_red = 0, n_halo = 0, n_p2p = 0;  // eig_comm_counters
   bool comm_always = false;          // EIG_COMM_ALWAYS: collectives through `comm` even at one rank
   bool halo_mailbox = false;         // eig_comm_select_halo(EIG_HALO_MAILBOX) beside RCCL
-  bool distributed() const { return nranks > 1 && (comm || loop || (mbox && mbox->ready)); }
+  bool loopback() const { return loop != nullptr; }
+  // the mailbox is open and validated / and allreduces go through it (eig_comm_select_allreduce)
+  bool mailbox_ready() const { return mbox && mbox->ready; }
+  bool mailbox_allreduce() const { return mailbox_ready() && mbox->on; }
+  const eigmi::Mailbox &mailbox_dev() const { return mbox->dev; }
+  bool distributed() const { return nranks > 1 && (comm || loop || mailbox_ready()); }
   // whether allreduces go through a transport (distributed, or a forced one-rank RCCL communicator)
-  bool collectives() const { return distributed() || (comm_always && (comm || (mbox && mbox->ready))); }
+  bool collectives() const { return distributed() || (comm_always && (comm || mailbox_ready())); }
   // the fused Lanczos step exchanges its three sums inside the step kernel (EIG_AR_MAILBOX_STEP)
-  bool step_exchange() const { return collectives() && mbox && mbox->ready && mbox->on && mbox->step; }
+  bool step_exchange() const { return collectives() && mailbox_allreduce() && mbox->step; }
   // reusable device buffers for drivers (grown on demand)
   std::vector<std::pair<void *, size_t>> pool;
   // a look-ahead MGS last launch (grid barriers without a cooperative launch) has been enqueued
@@ -689,10 +598,7 @@ void tri_upper_inv(int n, const double *R, double *Rinv);
 bool gen_eig(int n, const std::vector<double> &g, std::vector<std::complex<double>> &w,
              std::vector<std::complex<double>> &Y);
 
-// ---- helpers in api.cpp --------------------------------------------------------------------
-// Ghost entries of window vector x (and x2 when given) from their owners.
-// width: doubles per row of x (2 for the fused step's interleaved pair vectors).
-void halo_exchange(const eig_mat_s &A, double *x, hipStream_t s, double *x2 = nullptr, int width = 1);
+// ---- helpers in api.cpp (those of comm.cpp: comm.h) ------------------------------------------
 void mv_device(eig_mat_s &A, double *x, double *y);
 void gram_device(eig_ctx_t ctx, i64 n, i64 m1, i64 m2, const double *Q1, const double *Q2, double *G);
 // gram0 (or null): the window Gram of the first 8-column block, already summed by the caller's
@@ -704,12 +610,6 @@ void spmm_dot_gram_device(const eig_mat_s &A, const double *X, double *Y, double
 void b_orthonormalize_device(eig_mat_s &B, i64 m, double *Q, double *norm);
 // Host CSR copy of a single-rank matrix's device image (rows in ISTL order, padding dropped).
 void mat_download_bcsr(const eig_mat_s &A, std::vector<i64> &rowptr, std::vector<i32> &col, std::vector<double> &vals);
-void allreduce_sum(eig_ctx_t ctx, double *buf, i64 count, hipStream_t s);
-// Whether allreduce_sum_red can run on ctx->red_stream concurrently with the compute and halo
-// streams (RCCL with the split communicator, or the mailbox); false for one rank / loopback.
-bool allreduce_overlaps(eig_ctx_t ctx);
-// allreduce_sum on the split communicator (or the mailbox), for ctx->red_stream.
-void allreduce_sum_red(eig_ctx_t ctx, double *buf, i64 count, hipStream_t s);
 void *ctx_buffer(eig_ctx_t ctx, int slot, size_t bytes);
 void host_random_normal(i64 count, unsigned seed, double *out);
 
@@ -759,5 +659,28 @@ struct DevBuf {
   DevBuf &operator=(const DevBuf &) = delete;
   double *d() const { return static_cast<double *>(p); }
 };
+
+// Makes `dev` the current device for a scope (C entry points).
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev)
+  {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) EIG_HIP(hipSetDevice(dev));
+  }
+  ~DeviceGuard()
+  {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+template <class T>
+T *dev_alloc(size_t count)
+{
+  void *p = nullptr;
+  if (count == 0) count = 1;
+  EIG_HIP(hipMalloc(&p, count * sizeof(T)));
+  return static_cast<T *>(p);
+}
 
 }  // namespace eigmi

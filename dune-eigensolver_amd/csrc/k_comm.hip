@@ -90,7 +90,7 @@ void launch_mailbox_allreduce(double *buf, int count, const Mailbox &mb, unsigne
 }
 
 // ---------------------------------------------------------------------------------------------
-// The halo exchange of mailbox-only ranks over the same IPC mappings (HaloBox, internal.h): the
+// The halo exchange of mailbox-only ranks over the same IPC mappings (HaloBox, comm.h): the
 // boundary rows a peer needs are stored straight into that peer's uncached staging slot over xGMI,
 // and the ghost rows are copied out of my own staging once every peer's sequence line carries the
 // exchange's number.  Two launches on the exchange stream:

@@ -1111,7 +1111,7 @@ void launch_lanczos_fused(const eig_mat_s &A, const double *P, double *Pout, con
   {
     EIG_CHECK(A.ctx->step_exchange(), EIG_ERR_ARG, "fused step: in-kernel exchange without the mailbox");
     fa.xch = fl.xch & kXchPublish;
-    fa.mb = A.ctx->mbox->dev;
+    fa.mb = A.ctx->mailbox_dev();
   }
 #define EIG_LFB(B_)                                                                                          \
   if (A.br == B_)                                                                                            \

@@ -1,4 +1,4 @@
-// One-GPU rehearsal of the RCCL point-to-point pattern of the halo exchange (api.cpp halo_exchange:
+// One-GPU rehearsal of the RCCL point-to-point pattern of the halo exchange (comm.cpp halo_exchange:
 // ncclGroupStart; ncclRecv...; ncclSend...; ncclGroupEnd on a non-blocking stream), with a one-rank
 // communicator whose only peer is rank 0 itself: one boundary plane of the 256^3 split (65,536
 // doubles = 512 KiB, the classic step) and one plane of (t, u) pairs (1 MiB, the fused step), on the
