@@ -1,7 +1,7 @@
 // api.cpp -- the C ABI of libeigmi (include/eigmi.h): contexts, device memory, upload of a matrix's
 // host images (built by mat_image.cpp: SELL-64, symmetric band, slice split), the halo plan of
 // row-partitioned matrices, BlockVector and MultiVector operations.  Drivers live in drivers.cpp,
-// the transports and their entry points in comm.cpp.
+// the transports and their entry points in comm.cpp, the Gram and the orthonormalisations in orth.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -18,7 +18,7 @@ using namespace eigmi;
 // ============================================================================================
 namespace eigmi {
 
-void *ctx_buffer(eig_ctx_t ctx, int slot, size_t bytes)
+void *ctx_buffer(eig_ctx_t ctx, CtxSlot slot, size_t bytes)
 {
   if ((int)ctx->pool.size() <= slot) ctx->pool.resize(slot + 1, {nullptr, 0});
   auto &e = ctx->pool[slot];
@@ -132,7 +132,7 @@ extern "C" int eig_ctx_destroy(eig_ctx_t ctx)
   if (!ctx) return EIG_OK;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->mgs_err_host) (void)hipHostFree(ctx->mgs_err_host);
+  mgs_release(ctx);
   comm_destroy(ctx);
   for (auto &e : ctx->pool)
     if (e.first) (void)hipFree(e.first);
@@ -689,8 +689,8 @@ extern "C" int eig_mv_host(eig_mat_t A, const double *xh, double *yh)
     DeviceGuard dg(A->ctx->device);
     eig_ctx_t ctx = A->ctx;
     const size_t wb = (size_t)A->window * sizeof(double);
-    double *x = (double *)ctx_buffer(ctx, 0, wb);
-    double *y = (double *)ctx_buffer(ctx, 1, wb);
+    double *x = (double *)ctx_buffer(ctx, kSlotMvHostX, wb);
+    double *y = (double *)ctx_buffer(ctx, kSlotMvHostY, wb);
     const i64 n = A->nb_rows * A->br;
     if (A->nb_rows_global == A->nb_rows && !ctx->distributed())
     {
@@ -801,10 +801,7 @@ extern "C" int eig_stream_copy_timed(eig_ctx_t ctx, int64_t n, const double *x, 
 // ============================================================================================
 // MultiVector<double,8>
 // ============================================================================================
-#define EIG_MV8_CHECK(m)                                                                             \
-  EIG_CHECK((m) % 8 == 0, EIG_ERR_SHAPE, "number of cols must be a multiple of block size");       \
-  EIG_CHECK((m) >= 0, EIG_ERR_ARG, "negative column count")
-
+// (the Gram and the orthonormalisations: orth.cpp)
 extern "C" int eig_spmm_mv8(eig_mat_t A, int64_t m, const double *Qin, double *Qout)
 {
   return guard(A ? A->ctx : nullptr, [&] {
@@ -863,239 +860,6 @@ extern "C" int eig_dot_diag_mv8(eig_ctx_t ctx, int64_t n, int64_t m, const doubl
   });
 }
 
-namespace eigmi {
-// G (m1 x m2 row-major) = Q1^T Q2, tiled so that one launch stays within the ticket pool.
-void gram_device(eig_ctx_t ctx, i64 n, i64 m1, i64 m2, const double *Q1, const double *Q2, double *G)
-{
-  if (gram_mv8_chunks(m1, m2) <= 48)
-  {
-    launch_gram_mv8(n, m1, m2, Q1, Q2, G, 0, ctx->stream, ctx->red);
-  }
-  else
-  {
-    // row panels of Q1 (32 columns each) against all of Q2; write into a temp then scatter
-    EIG_CHECK(gram_mv8_chunks(32, m2) <= 48, EIG_ERR_ARG, "gram: Q2 too wide (> 1536 columns)");
-    double *tmp = (double *)ctx_buffer(ctx, 2, (size_t)32 * m2 * sizeof(double));
-    for (i64 r = 0; r < m1; r += 32)
-    {
-      const i64 mr = std::min<i64>(32, m1 - r);
-      launch_gram_mv8(n, mr, m2, Q1 + r * n, Q2, tmp, 0, ctx->stream, ctx->red);
-      EIG_HIP(hipMemcpyAsync(G + r * m2, tmp, mr * m2 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-  }
-  allreduce_sum(ctx, G, m1 * m2, ctx->stream);
-}
-
-
-void spmm_dot_gram_device(const eig_mat_s &A, const double *X, double *Y, double *dp, double *gram)
-{
-  eig_ctx_t ctx = A.ctx;
-  if (launch_spmm_dot_gram_mv8(A, 8, X, Y, dp, gram, ctx->stream, ctx->red)) return;
-  // no fused kernel on this image: the product with its dots, then the panel Gram of the block
-  launch_spmm_dot_mv8(A, 8, X, Y, dp, ctx->stream, ctx->red);
-  gram_device(ctx, A.nb_rows * A.br, 8, 8, Y, Y, gram);  // scalar rows
-}
-
-void orthonormalize_device(eig_ctx_t ctx, i64 n, i64 m, double *Q, int variant, const double *gram0)
-{
-  const int flags = variant & (EIG_ORTHO_GRID | EIG_ORTHO_NO_COOP | EIG_ORTHO_ONE_WG);
-  const int la = (variant >> EIG_ORTHO_LOOKAHEAD_SHIFT) & 15;  // EIG_ORTHO_LOOKAHEAD(L); 0: the default
-  const int L = la ? std::min(la, 8) : mgs_lookahead_default();
-  variant &= 0xff;
-  hipStream_t s = ctx->stream;
-  double *S = (double *)ctx_buffer(ctx, 3, 64 * sizeof(double));
-  double *U = S + 0;  // reused: Ssum for MGS, Gram for CholQR
-  double *U2 = (double *)ctx_buffer(ctx, 4, 64 * sizeof(double));
-  double *Sg = nullptr;
-  if (m > 8) Sg = (double *)ctx_buffer(ctx, 5, (size_t)8 * m * sizeof(double));
-  for (i64 bk = 0; bk < m; bk += 8)
-  {
-    double *Qb = Q + bk * n;
-    if (bk == 0 && gram0 && variant == EIG_ORTHO_MGS && !ctx->distributed() && L == 8 &&
-        launch_mgs_lookahead_gram(ctx, n, Qb, gram0, s))
-    {
-      // (the block's first read pass replaced by the Gram the caller's product summed)
-    }
-    else if (variant == EIG_ORTHO_MGS && !ctx->distributed() && (flags & EIG_ORTHO_ONE_WG) && !(flags & EIG_ORTHO_GRID) &&
-        launch_mgs_small(n, Qb, s))
-    {
-    }
-    else if (variant == EIG_ORTHO_MGS && !ctx->distributed() && !(flags & EIG_ORTHO_GRID) &&
-             launch_mgs_coop(ctx, n, Qb, S, s))
-    {
-    }
-    else if (variant == EIG_ORTHO_MGS && !ctx->distributed() && launch_mgs_lookahead(ctx, n, Qb, L, !(flags & EIG_ORTHO_NO_COOP), s))
-    {
-    }
-    else if (variant == EIG_ORTHO_MGS)
-    {
-      for (int k = 0; k <= 8; ++k)
-      {
-        launch_mgs_pass(n, Qb, k, S, 0, s, ctx->red);
-        if (k < 8) allreduce_sum(ctx, S + 8 * k, 8, s);
-      }
-    }
-    else
-    {
-      gram_device(ctx, n, 8, 8, Qb, Qb, U);
-      launch_cholqr_factor(U, U2, nullptr, 0, s);
-      launch_apply_upper(n, Qb, U2, s);
-    }
-    const i64 mrest = m - bk - 8;
-    if (mrest > 0 && variant == EIG_ORTHO_CHOLQR_SPLIT)
-    {
-      // orthonormalize_avx2_b8 (kernels_avx2.hh:255-381): columns 0-3 of Q_bk first, then 4-7
-      // against the updated later blocks.  Each half is the full 8 x mrest Gram with the other
-      // half's rows zeroed: those add 0 * q_k, which leaves every entry exactly as it was.
-      for (int h = 0; h < 2; ++h)
-      {
-        gram_device(ctx, n, 8, mrest, Qb, Qb + 8 * n, Sg);
-        EIG_HIP(hipMemsetAsync(Sg + (h ? 0 : 4 * mrest), 0, (size_t)4 * mrest * sizeof(double), s));
-        launch_project(n, mrest, Qb, Qb + 8 * n, Sg, s);
-      }
-    }
-    else if (mrest > 0)
-    {
-      gram_device(ctx, n, 8, mrest, Qb, Qb + 8 * n, Sg);
-      launch_project(n, mrest, Qb, Qb + 8 * n, Sg, s);
-    }
-  }
-}
-}  // namespace eigmi
-
-extern "C" int eig_gram_mv8(eig_ctx_t ctx, int64_t n, int64_t m1, int64_t m2, const double *Q1, const double *Q2,
-                            double *G)
-{
-  return guard(ctx, [&] {
-    EIG_CHECK(ctx && Q1 && Q2 && G && n >= 0, EIG_ERR_ARG, "eig_gram_mv8: bad argument");
-    EIG_MV8_CHECK(m1);
-    EIG_MV8_CHECK(m2);
-    DeviceGuard dg(ctx->device);
-    if (m1 > 0 && m2 > 0) gram_device(ctx, n, m1, m2, Q1, Q2, G);
-  });
-}
-
-extern "C" int eig_orthonormalize_mv8(eig_ctx_t ctx, int64_t n, int64_t m, double *Q, int variant)
-{
-  return guard(ctx, [&] {
-    EIG_CHECK(ctx && Q && n >= 0, EIG_ERR_ARG, "eig_orthonormalize_mv8: bad argument");
-    const int v = variant & 0xff;
-    EIG_CHECK(v == EIG_ORTHO_MGS || v == EIG_ORTHO_CHOLQR || v == EIG_ORTHO_CHOLQR_SPLIT, EIG_ERR_ARG,
-              "unknown variant");
-    EIG_CHECK((variant & ~(0xff | EIG_ORTHO_GRID | EIG_ORTHO_NO_COOP | EIG_ORTHO_ONE_WG | (15 << EIG_ORTHO_LOOKAHEAD_SHIFT))) == 0 &&
-                  ((variant >> EIG_ORTHO_LOOKAHEAD_SHIFT) & 15) <= 8,
-              EIG_ERR_ARG, "unknown variant flags");
-    EIG_MV8_CHECK(m);
-    DeviceGuard dg(ctx->device);
-    orthonormalize_device(ctx, n, m, Q, variant);
-  });
-}
-
-extern "C" int eig_orthonormalize_gram_mv8(eig_ctx_t ctx, int64_t n, int64_t m, double *Q, const double *gram)
-{
-  return guard(ctx, [&] {
-    EIG_CHECK(ctx && Q && gram && n >= 0, EIG_ERR_ARG, "eig_orthonormalize_gram_mv8: bad argument");
-    EIG_MV8_CHECK(m);
-    DeviceGuard dg(ctx->device);
-    orthonormalize_device(ctx, n, m, Q, EIG_ORTHO_MGS, gram);
-  });
-}
-
-extern "C" int eig_spmm_dot_gram_mv8(eig_mat_t mat, int64_t m, const double *Qin, double *Qout, double *dp,
-                                     double *gram)
-{
-  return guard(mat ? mat->ctx : nullptr, [&] {
-    EIG_CHECK(mat && Qin && Qout && dp && gram, EIG_ERR_ARG, "eig_spmm_dot_gram_mv8: bad argument");
-    EIG_CHECK(m == 8, EIG_ERR_SHAPE, "eig_spmm_dot_gram_mv8: one 8-column block (m = 8)");
-    EIG_CHECK(mat->br == 1 && mat->bc == 1, EIG_ERR_BLOCKSIZE,
-              "matmul_sparse_tallskinny_blocked: only implemented for FieldMatrix<..,1,1>");
-    DeviceGuard dg(mat->ctx->device);
-    spmm_dot_gram_device(*mat, Qin, Qout, dp, gram);
-  });
-}
-
-extern "C" int eig_orthonormalize_passes(eig_ctx_t ctx, int *passes)
-{
-  return guard(ctx, [&] {
-    EIG_CHECK(ctx && passes, EIG_ERR_ARG, "eig_orthonormalize_passes: null argument");
-    DeviceGuard dg(ctx->device);
-    *passes = mgs_lookahead_passes(ctx);
-  });
-}
-
-extern "C" int eig_orthonormalize_naive(eig_ctx_t ctx, int64_t n, int64_t m, double *Q)
-{
-  return guard(ctx, [&] {
-    EIG_CHECK(ctx && Q && n >= 0 && m >= 0, EIG_ERR_ARG, "eig_orthonormalize_naive: bad argument");
-    EIG_CHECK(m <= 512, EIG_ERR_ARG, "eig_orthonormalize_naive: at most 512 columns");
-    DeviceGuard dg(ctx->device);
-    hipStream_t s = ctx->stream;
-    double *d = (double *)ctx_buffer(ctx, 6, (size_t)(m + 1) * sizeof(double));
-    // kernels_cpp.hh:128-154: normalise q_k, then q_j -= (q_k . q_j) q_k for every j > k.
-    for (i64 k = 0; k < m; ++k)
-    {
-      double *qk = Q + k * n;
-      launch_nrm2sq(n, qk, d + m, 0, s, ctx->red);
-      allreduce_sum(ctx, d + m, 1, s);
-      launch_scal_dev(n, d + m, true, qk, s);
-      const i64 rest = m - k - 1;
-      for (i64 j0 = 0; j0 < rest; j0 += 8 * 48)
-      {
-        const int kk = (int)std::min<i64>(rest - j0, 8 * 48);
-        launch_gemv_t(n, kk, Q + (k + 1 + j0) * n, n, qk, d + j0, 0, s, ctx->red);
-      }
-      allreduce_sum(ctx, d, rest, s);
-      // q_j -= d_j q_k : rank-1 update, one axpy per column (same rounding as the reference)
-      for (i64 j = 0; j < rest; ++j) launch_axpy_dev(n, d + j, -1.0, qk, Q + (k + 1 + j) * n, s);
-    }
-  });
-}
-
-namespace eigmi {
-// B_orthonormalize_blocked (kernels_cpp.hh:356-591) on the device; *norm (device) receives the
-// max off-diagonal R coefficient.
-void b_orthonormalize_device(eig_mat_s &B, i64 m, double *Q, double *norm)
-{
-  eig_ctx_t ctx = B.ctx;
-  hipStream_t s = ctx->stream;
-  const i64 n = B.nb_rows;
-  double *P = (double *)ctx_buffer(ctx, 7, (size_t)n * 8 * sizeof(double));
-  double *G = (double *)ctx_buffer(ctx, 3, 64 * sizeof(double));
-  double *U = (double *)ctx_buffer(ctx, 4, 64 * sizeof(double));
-  double *Sg = m > 8 ? (double *)ctx_buffer(ctx, 5, (size_t)8 * m * sizeof(double)) : nullptr;
-  EIG_HIP(hipMemsetAsync(norm, 0, sizeof(double), s));
-  for (i64 bk = 0; bk < m; bk += 8)
-  {
-    double *Qb = Q + bk * n;
-    launch_spmm_mv8(B, 8, Qb, P, s);                   // P = B Q_bk          (:378-395)
-    gram_device(ctx, n, 8, 8, P, Qb, G);               // s = P^T Q_bk        (:450-456)
-    launch_cholqr_factor(G, U, norm, 1, s);            // mirror upper, norm, U (:457-526)
-    launch_apply_upper(n, Qb, U, s);                   // Q_bk := Q_bk U      (:528-539)
-    launch_apply_upper(n, P, U, s);                    // P := P U            (:540-552)
-    const i64 mrest = m - bk - 8;
-    if (mrest > 0)
-    {
-      gram_device(ctx, n, 8, mrest, P, Qb + 8 * n, Sg);  // S = P^T Q_bj     (:559-565)
-      launch_max_offdiag(Sg, 8, mrest, false, norm, s);  // norm (:566-568)
-      launch_project(n, mrest, Qb, Qb + 8 * n, Sg, s);   // Q_bj -= Q_bk S   (:570-584)
-    }
-  }
-}
-}  // namespace eigmi
-
-extern "C" int eig_b_orthonormalize_mv8(eig_mat_t B, int64_t m, double *Q, double *norm)
-{
-  return guard(B ? B->ctx : nullptr, [&] {
-    EIG_CHECK(B && Q && norm, EIG_ERR_ARG, "eig_b_orthonormalize_mv8: null argument");
-    EIG_CHECK(B->br == 1 && B->bc == 1, EIG_ERR_BLOCKSIZE,
-              "B_orthonormalize_blocked: only implemented for FieldMatrix<..,1,1>");
-    EIG_MV8_CHECK(m);
-    EIG_CHECK(!B->ctx->distributed(), EIG_ERR_ARG, "eig_b_orthonormalize_mv8: single rank only");
-    DeviceGuard dg(B->ctx->device);
-    b_orthonormalize_device(*B, m, Q, norm);
-  });
-}
-
 extern "C" int eig_random_mv8(eig_ctx_t ctx, int64_t n, int64_t m, unsigned seed, double *Q)
 {
   return guard(ctx, [&] {
@@ -1108,26 +872,6 @@ extern "C" int eig_random_mv8(eig_ctx_t ctx, int64_t n, int64_t m, unsigned seed
     EIG_HIP(hipMemcpyAsync(Q, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     EIG_HIP(hipStreamSynchronize(ctx->stream));
   });
-}
-
-extern "C" double eig_flops_orthonormalize(int64_t n, int64_t m)
-{
-  // kernels_cpp.hh:98-106
-  double f = 0.0;
-  for (i64 k = m; k > 0; k--) f += 2.0 * n + n + (k - 1) * 4.0 * n;
-  return f;
-}
-
-extern "C" double eig_bytes_orthonormalize_blocked(int64_t n, int64_t m, int b)
-{
-  // kernels_cpp.hh:157-175
-  double c = 0.0;
-  for (i64 bk = 0; bk < m; bk += b)
-  {
-    for (int k = b; k > 0; k--) c += (double)n * k + (double)n * (1 + (k - 1) + 1);
-    for (i64 bj = bk + b; bj < m; bj += b) c += 5.0 * b * n;
-  }
-  return c * 8;
 }
 
 // ============================================================================================

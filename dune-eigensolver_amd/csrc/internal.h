@@ -40,6 +40,16 @@ struct Error : std::runtime_error {
 // Streaming kernels use this many workgroups (8 per CU x 256 CUs) and grid-stride inside.
 constexpr int kStreamBlocks = 2048;
 constexpr int kStreamThreads = 256;
+// grid of a grid-stride launch: one workgroup per `per_block` units of work, 1 .. cap
+static inline int grid_for(i64 work, i64 per_block, int cap)
+{
+  i64 g = (work + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  return (int)(g < cap ? g : cap);
+}
+// 32- and 16-byte vectors of doubles (MFMA accumulators, 16-B loads and stores)
+typedef double d4 __attribute__((ext_vector_type(4)));
+typedef double dv2 __attribute__((ext_vector_type(2)));
 // Reduction workspace: per-block partials (sc1 stores) + one ticket per concurrent reduction.
 constexpr int kMaxRedBlocks = 2048;
 constexpr int kMaxRedVals = 256;   // values reduced by one launch (e.g. a 16x16 Gram tile)
@@ -60,6 +70,7 @@ struct ReduceWS {
 }  // namespace eigmi
 
 #include "comm.h"  // the transport structures of eig_ctx_s and what comm.cpp offers
+#include "orth.h"  // the look-ahead MGS member of eig_ctx_s and what k_orth.hip / orth.cpp offer
 
 struct eig_mg_s;  // mg.cpp
 
@@ -95,16 +106,8 @@ struct eig_ctx_s {
   // the fused Lanczos step exchanges its three sums inside the step kernel (EIG_AR_MAILBOX_STEP)
   bool step_exchange() const { return collectives() && mailbox_allreduce() && mbox->step; }
   // reusable device buffers for drivers (grown on demand)
-  std::vector<std::pair<void *, size_t>> pool;
-  // a look-ahead MGS last launch (grid barriers without a cooperative launch) has been enqueued
-  // since the last mgs_lookahead_check: its sticky error word must be read at the next sync point
-  bool mgs_la_armed = false;
-  // its sticky error word in page-locked, device-mapped host memory: the kernel stores into it, the
-  // host reads it after any stream synchronisation without a copy (allocated at first use)
-  int *mgs_err_host = nullptr, *mgs_err_dev = nullptr;
-  // the window Gram whose product also zeroed the look-ahead MGS's barrier word (launch_spmm_dot_gram_mv8);
-  // consumed by the next launch_mgs_lookahead_gram of that Gram
-  const double *mgs_bar_clean = nullptr;
+  std::vector<std::pair<void *, size_t>> pool;  // indexed by eigmi::CtxSlot (ctx_buffer)
+  eigmi::MgsCtx mgs;  // host side of the look-ahead MGS (orth.h)
 };
 
 namespace eigmi {
@@ -323,8 +326,6 @@ bool launch_box_spmm_dot_gram(const eig_mat_s &A, i64 m, const double *X, double
                               ReduceWS red, hipStream_t s, unsigned *zero_word = nullptr);
 bool launch_spmm_march_dot_gram(const eig_mat_s &A, i64 m, const double *X, double *Y, double *dp, double *gram,
                                 ReduceWS red, hipStream_t s, unsigned *zero_word = nullptr);
-// the look-ahead MGS state's barrier word of this context (allocated and zeroed on first use)
-unsigned *mgs_lookahead_barrier(eig_ctx_t ctx);
 // StandardLargest's product: Y = A X, dp = diag(X^T Y) and (gram != null, m = 8) the window Gram of Y
 // for the next iteration's MGS; false when no fused kernel applies (then gram is not written).
 bool launch_spmm_dot_gram_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, double *dp, double *gram,
@@ -408,34 +409,7 @@ void launch_spmm_dot_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, 
                          ReduceWS red);
 void launch_dot_diag_mv8(i64 n, i64 m, const double *Q1, const double *Q2, double *dp, int ticket,
                          hipStream_t s, ReduceWS red);
-void launch_gram_mv8(i64 n, i64 m1, i64 m2, const double *Q1, const double *Q2, double *G, int ticket,
-                     hipStream_t s, ReduceWS red);
-int gram_mv8_chunks(i64 m1, i64 m2);  // tickets one launch_gram_mv8 takes
-// The same Gram on window-layout panels (column blocks ld rows apart, pointers at owned row 0).
-void launch_gram_panel(eig_ctx_t ctx, i64 n, i64 ld, i64 m1, i64 m2, const double *Q1, const double *Q2, double *G,
-                       hipStream_t s);
-// Block Gram-Schmidt building blocks, see k_mv8.hip.
-void launch_mgs_pass(i64 n, double *Qb, int k, double *S, int ticket, hipStream_t s, ReduceWS red);
-// MGS with Gram look-ahead (k_mv8.hip): L steps per read pass, gated; false when L <= 1 or n <= 0
-constexpr int kMgsLookaheadDefault = 8;
-int mgs_lookahead_default();  // EIGMI_MGS_LOOKAHEAD or kMgsLookaheadDefault
-bool launch_mgs_lookahead(eig_ctx_t ctx, i64 n, double *Qb, int L, bool coop, hipStream_t s);
-// The look-ahead MGS of one 8-column block whose window Gram G (8 x 8 row-major, device) is already
-// known: the first read pass is replaced by G (k_mgs_la_gram), then the last launch as usual.
-bool launch_mgs_lookahead_gram(eig_ctx_t ctx, i64 n, double *Qb, const double *G, hipStream_t s);
-int mgs_lookahead_passes(eig_ctx_t ctx);  // read passes of the last call (-1: none finished)
-// After the stream is synchronised: throw EIG_ERR_HIP (and clear the sticky flag) when a look-ahead
-// MGS last launch since the previous check timed out in its grid barrier (its rows are NaN)
-void mgs_lookahead_check(eig_ctx_t ctx);
-// Whole column MGS of one 8-column block in one workgroup (n <= 4096, one rank); false = not taken.
-bool launch_mgs_small(i64 n, double *Qb, hipStream_t s);
-// The 9 read-only MGS passes in one cooperative launch with grid barriers (k_mv8.hip k_mgs_coop; one
-// rank); false = refused or timed out (nothing written): run the per-pass launches instead
-bool launch_mgs_coop(eig_ctx_t ctx, i64 n, double *Qb, double *Ssum, hipStream_t s);
-void launch_apply_upper(i64 n, double *Qb, const double *U, hipStream_t s);
-void launch_cholqr_factor(const double *G, double *U, double *normmax, int flags, hipStream_t s);
-void launch_project(i64 n, i64 mrest, const double *Qk, double *Qrest, const double *S, hipStream_t s);
-void launch_max_offdiag(const double *S, i64 rows, i64 cols, bool upper_only, double *normmax, hipStream_t s);
+// (the Gram panel and the block Gram-Schmidt building blocks of k_orth.hip: orth.h)
 
 // Column-major (b = 1) GEMV-type helpers for the Lanczos re-orthogonalisation:
 // c = V^T w (V: k columns of length ld, owned slice at off), w -= V c.
@@ -521,7 +495,7 @@ void launch_lobpcg_update(eig_ctx_t ctx, i64 n, i64 ld, i64 m, int kb, double *S
 void mg_apply(eig_mg_s &mg, i64 m, const double *B, double *X, int cycles);
 eig_mat_s *mg_matrix(const eig_mg_s &mg);
 int mg_max_cols(const eig_mg_s &mg);
-// CholQR2's middle step, b = 32: Z <- Z S, G = (Z S)^T (MZ S) (k_block.hip; partials in context slot 8)
+// CholQR2's middle step, b = 32: Z <- Z S, G = (Z S)^T (MZ S) (k_block.hip; partials in kSlotPanelPartials)
 void launch_cholqr_fold(eig_ctx_t ctx, i64 n, i64 ld, double *Z, const double *MZ, const double *S, double *G,
                         hipStream_t s);
 void launch_chol_small(int b, int pass, const double *G, double *R, double *Ri, double *Rtot, int *flag,
@@ -598,19 +572,31 @@ void tri_upper_inv(int n, const double *R, double *Rinv);
 bool gen_eig(int n, const std::vector<double> &g, std::vector<std::complex<double>> &w,
              std::vector<std::complex<double>> &Y);
 
-// ---- helpers in api.cpp (those of comm.cpp: comm.h) ------------------------------------------
+// ---- helpers in api.cpp (those of comm.cpp: comm.h, of orth.cpp: orth.h) ----------------------
 void mv_device(eig_mat_s &A, double *x, double *y);
-void gram_device(eig_ctx_t ctx, i64 n, i64 m1, i64 m2, const double *Q1, const double *Q2, double *G);
-// gram0 (or null): the window Gram of the first 8-column block, already summed by the caller's
-// product (eig_orthonormalize_gram_mv8; MGS look-ahead on one rank only, else ignored)
-void orthonormalize_device(eig_ctx_t ctx, i64 n, i64 m, double *Q, int variant, const double *gram0 = nullptr);
-// Y = A X (one 8-column block), dp = diag(X^T Y), gram = Y^T Y (8 x 8): fused into the product where a
-// kernel has the epilogue (launch_spmm_dot_gram_mv8), else product + panel Gram
-void spmm_dot_gram_device(const eig_mat_s &A, const double *X, double *Y, double *dp, double *gram);
-void b_orthonormalize_device(eig_mat_s &B, i64 m, double *Q, double *norm);
 // Host CSR copy of a single-rank matrix's device image (rows in ISTL order, padding dropped).
 void mat_download_bcsr(const eig_mat_s &A, std::vector<i64> &rowptr, std::vector<i32> &col, std::vector<double> &vals);
-void *ctx_buffer(eig_ctx_t ctx, int slot, size_t bytes);
+// The reusable device buffers of a context (eig_ctx_s::pool), one per slot, grown on demand and all used
+// on ctx->stream.  A slot belongs to the users named here; a new user takes a new slot.
+enum CtxSlot {
+  kSlotMvHostX = 0,        // eig_mv_host: the input vector in window layout
+  kSlotMvHostY = 1,        // eig_mv_host: the product in window layout
+  kSlotGramRows = 2,       // gram_device: a 32-row panel of a Gram too wide for one launch's tickets
+  kSlotOrthS = 3,          // orthonormalize_device / b_orthonormalize_device: the 8 x 8 MGS sums or CholQR Gram
+  kSlotOrthU = 4,          // the same two: the 8 x 8 CholQR factor
+  kSlotOrthProj = 5,       // the same two: the 8 x (m - 8) projection coefficients of the later blocks
+  kSlotNaiveDots = 6,      // eig_orthonormalize_naive: the m dots of a column and its squared norm
+  kSlotBOrthP = 7,         // b_orthonormalize_device: P = B Q_bk of the current block
+  // launch_gram_panel (k_orth.hip), panel_gram's two-stage form and launch_cholqr_fold (k_block.hip): the
+  // workgroup partials of one panel product.  Shared safely: all three run on ctx->stream, and a user's
+  // partials are dead when its own launch sequence ends (the kernel's last workgroup, or the second
+  // stage, has summed them into the caller's output), so the next user on the stream may overwrite them
+  kSlotPanelPartials = 8,
+  kSlotMgResidDots = 9,    // eig_mg_solve (mg.cpp): the column dots of the residual and the right-hand side
+  kSlotMgsCoop = 10,       // launch_mgs_coop (k_orth.hip): partials, barrier counter and error word
+  kSlotMgsLa = 11,         // mgs_lookahead_state (orth.cpp): the look-ahead MGS state, orth.h MgsLaState
+};
+void *ctx_buffer(eig_ctx_t ctx, CtxSlot slot, size_t bytes);
 void host_random_normal(i64 count, unsigned seed, double *out);
 
 }  // namespace eigmi

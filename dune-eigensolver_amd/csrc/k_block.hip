@@ -27,9 +27,6 @@
 
 namespace eigmi {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double dv2 __attribute__((ext_vector_type(2)));
-
 static inline int grid_cap(i64 work, i64 per_block, int cap)
 {
   i64 g = (work + per_block - 1) / per_block;
@@ -682,7 +679,7 @@ void panel_gram(eig_ctx_t ctx, i64 n, i64 ld, i64 m1, i64 m2, const double *Q1, 
   // at most 256 per output block so that stage 2 stays short
   const int gx = (int)std::max<i64>(1, std::min<i64>(std::min(256, std::max(1, 1024 / ny)), (n + 255) / 256));
   const size_t E = (size_t)TI * TJ * 256;
-  double *part = (double *)ctx_buffer(ctx, 8, (size_t)gx * ny * E * sizeof(double));  // slot 8: panel partials
+  double *part = (double *)ctx_buffer(ctx, kSlotPanelPartials, (size_t)gx * ny * E * sizeof(double));
   hipLaunchKernelGGL((k_panel_gram_part<TI, TJ>), dim3(gx, ny), dim3(256), 0, s, n, ld, (int)m1, (int)m2, nbj, Q1, Q2,
                      part);
   EIG_HIP(hipGetLastError());
@@ -692,7 +689,7 @@ void panel_gram(eig_ctx_t ctx, i64 n, i64 ld, i64 m1, i64 m2, const double *Q1, 
 }
 }  // namespace
 
-// The block Lanczos panel products run on the a6 Gram kernel (k_mv8.hip launch_gram_panel: paired
+// The block Lanczos panel products run on the a6 Gram kernel (k_orth.hip launch_gram_panel: paired
 // 16-column tiles, one launch with its deterministic two-level reduction); the two-launch form
 // above (k_panel_gram_part + k_panel_gram_reduce) is kept as launch_panel_gram_2stage for A/B.
 void launch_panel_gram(eig_ctx_t ctx, i64 n, i64 ld, i64 m1, i64 m2, const double *Q1, const double *Q2, double *G,
@@ -974,7 +971,7 @@ void launch_cholqr_fold(eig_ctx_t ctx, i64 n, i64 ld, double *Z, const double *M
   const i64 ntile = (n + 15) / 16;
   // two workgroups per CU (122 VGPRs + 48 AGPRs: two waves per SIMD)
   const int gx = (int)std::max<i64>(1, std::min<i64>(512, (ntile + 3) / 4));
-  double *part = (double *)ctx_buffer(ctx, 8, (size_t)(gx + 8) * E * sizeof(double));
+  double *part = (double *)ctx_buffer(ctx, kSlotPanelPartials, (size_t)(gx + 8) * E * sizeof(double));
   hipLaunchKernelGGL(k_cholqr_fold, dim3(gx), dim3(kFoldThreads), 0, s, n, ld, Z, MZ, S, G, part,
                      ctx->red.ticket(0));
   EIG_HIP(hipGetLastError());

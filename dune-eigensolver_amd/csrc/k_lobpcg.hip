@@ -15,9 +15,6 @@
 
 namespace eigmi {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double dv2 __attribute__((ext_vector_type(2)));
-
 // ---------------------------------------------------------------------------------------------
 // Residual.  Workgroup (x, y): column block y, rows strided by x; quad mapping (4 lanes per row,
 // lane cp holds columns 2 cp, 2 cp + 1: one wave instruction reads 16 whole 64-B rows).

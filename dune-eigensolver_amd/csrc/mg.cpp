@@ -495,7 +495,7 @@ extern "C" int eig_mg_solve(eig_mg_t mg, int64_t m, const double *B, double *X, 
       // max over columns of ||B - A X|| / ||B||
       MgLevel &L = mg->lev[0];
       double *T = L.T->d();
-      double *dp = (double *)ctx_buffer(ctx, 9, (size_t)2 * m * sizeof(double));
+      double *dp = (double *)ctx_buffer(ctx, kSlotMgResidDots, (size_t)2 * m * sizeof(double));
       launch_resid_mv8(*L.A, m, X, B, T, s);
       launch_dot_diag_mv8(L.n, m, T, T, dp, 0, s, ctx->red);
       launch_dot_diag_mv8(L.n, m, B, B, dp + m, 0, s, ctx->red);

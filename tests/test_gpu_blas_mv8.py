@@ -311,3 +311,34 @@ def test_spmm_dot_gram_pair(ctx, name):
     ctx.sync()
     ref = oracle.orthonormalize_mv8(Yh, n, m)
     assert np.abs(Y.get() - ref).max() < 1e-12 * max(1.0, np.abs(ref).max())
+
+
+@pytest.mark.parametrize("N", [8, 40], ids=["one_workgroup", "two_workgroups"])
+def test_spmm_dot_gram_handover_cleared(N):
+    """The hand-over between the product that sums the window Gram and the MGS that consumes it, when an
+    MGS of another block comes between them.  On a FRESH context (the product, not the MGS, allocates the
+    look-ahead state): eig_spmm_dot_gram_mv8, then eig_orthonormalize_mv8 of an unrelated block (which
+    clears the hand-over), then eig_orthonormalize_gram_mv8 with the product's Gram -- k_mgs_la_gram and the
+    last launch, not the one-launch hand-over of test_spmm_dot_gram_pair.  laplace2d(8): n = 64, one
+    look-ahead workgroup; laplace2d(40): n = 1600 > 1024, two workgroups, so the grid barrier is crossed.
+    Within 1e-12 of the restated orthonormalize_blocked of the product, and no barrier timeout (-2)."""
+    A = oracle.laplace2d(N)
+    n, m = A.n, 8
+    c = eigmi.Context(0)
+    try:
+        M = eigmi.Matrix.from_bcsr(c, A.rowptr, A.col, A.val)
+        X, Y, dp, G = c.array(oracle.random_mv8(n, m, 31)), c.zeros(n * m), c.zeros(8), c.zeros(64)
+        eigmi.spmm_dot_gram_mv8(M, m, X, Y, dp, G)
+        Yh = Y.get()
+        Z = c.array(oracle.random_mv8(n, m, 77))
+        eigmi.orthonormalize_mv8(c, n, m, Z, eigmi.ORTHO_MGS)
+        eigmi.orthonormalize_gram_mv8(c, n, m, Y, G)
+        c.sync()
+        passes = eigmi.orthonormalize_passes(c)
+        ref = oracle.orthonormalize_mv8(Yh, n, m)
+        diff = np.abs(Y.get() - ref).max()
+        print(f"hand-over cleared n={n}: {passes} read passes, |Q - Q_ref| = {diff:.2e}")
+        assert diff < 1e-12 * max(1.0, np.abs(ref).max())
+        assert passes != -2
+    finally:
+        c.close()
