@@ -547,7 +547,7 @@ extern "C" int eig_mat_kernel_info(eig_mat_t A, int op, char *name, int name_len
 {
   return guard(A ? A->ctx : nullptr, [&] {
     EIG_CHECK(A && name && name_len > 0, EIG_ERR_ARG, "eig_mat_kernel_info: null argument");
-    EIG_CHECK(op >= EIG_OP_SPMV && op <= EIG_OP_CHEB32, EIG_ERR_ARG, "eig_mat_kernel_info: bad op");
+    EIG_CHECK(op >= EIG_OP_SPMV && op <= EIG_OP_FILT32, EIG_ERR_ARG, "eig_mat_kernel_info: bad op");
     const std::string nm = kernel_for(*A, op);
     const size_t k = std::min<size_t>(nm.size(), (size_t)name_len - 1);
     std::memcpy(name, nm.data(), k);

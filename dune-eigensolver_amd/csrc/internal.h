@@ -438,6 +438,19 @@ void launch_cheb_step(const eig_mat_s &M, i64 m, const double *Xk, double *Xold,
 // kernel launches per launch_cheb_step call on M: sell_mv8_launches(m) for 1x1 blocks, one for the
 // blocked kernel
 int cheb_step_launches(const eig_mat_s &M, i64 m);
+// One Clenshaw step of the Chebyshev window filter (filter_host.h) fused into the product, with acc = A Xk:
+//     out = s1 acc + s0 Xk + s2 Xold + g B
+// written in place over Xold, which is read only when s2 != 0 (its contents are ignored otherwise: the filter's
+// first two steps).  Xold is neither Xk nor B.  One rank, square matrix; dispatch as launch_cheb_step: square
+// blocks 2..4 (k_spmm_blk_mv8_filt), the row-class / box image (kBoxFilt), else the SELL kernels (kFilt) -- the
+// general band march has no filter epilogue.
+void launch_filt_step(const eig_mat_s &A, i64 m, const double *Xk, double *Xold, const double *B, double s1,
+                      double s0, double s2, double g, hipStream_t s);
+int filt_step_launches(const eig_mat_s &A, i64 m);  // kernel launches per launch_filt_step call on A
+void launch_filt_step_blk(const eig_mat_s &A, i64 m, const double *Xk, double *Xold, const double *B, double s1,
+                          double s0, double s2, double g, hipStream_t s);
+bool launch_box_filt(const eig_mat_s &A, i64 m, const double *Xk, double *Xold, const double *B, double s1, double s0,
+                     double s2, double g, hipStream_t s);
 // The same step on square blocks 2..4 (k_mv8.hip k_spmm_blk_mv8_cheb; one rank, R = 1, square matrix):
 // launch_cheb_step dispatches here.  Vectors have nb_rows * br scalar rows, dinv is the scalar diagonal's.
 void launch_cheb_step_blk(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, const double *B,

@@ -46,7 +46,13 @@ static inline int grid_cap(i64 work, i64 per_block, int cap)
 // (Measured and dropped: a lane-per-row mapping with 16 columns per matrix pass -- 131 vs 119 us
 // for the 7-point SpMM at 128^3 -- and 2 column blocks per quad pass.)
 // ---------------------------------------------------------------------------------------------
-enum { kStore = 0, kCheb = 1, kResid = 2 };  // kResid: Y = B - A X (multigrid residual)
+//
+// kFilt epilogue (one Clenshaw step of the Chebyshev window filter, filter_host.h): with acc = (A x_k)_r,
+//     out[r] = s1 acc + s0 x_k[r] + s2 x_old[r] + g b[r]
+// written in place over x_old (Y); s2 == 0 (the filter's first two steps) reads no x_old.  The scalars
+// are kernel arguments (s1, s0 in the omega / gamma slots, then fs2, fg); no dinv stream.  Fused
+// multiply-adds and the zeroed non-stored entries of kCheb: tolerance-checked, not bitwise.
+enum { kStore = 0, kCheb = 1, kResid = 2, kFilt = 3 };  // kResid: Y = B - A X (multigrid residual)
 
 // Quad mapping: 4 lanes per row (lane owns column pair 2 (l & 3), 2 (l & 3) + 1 of every column
 // block), 16 rows per wave, a workgroup (4 waves) per 64-row slice, MB column blocks per matrix
@@ -70,7 +76,7 @@ __global__ __launch_bounds__(64 * W) void k_sell_mv8q(i64 nrows, i64 nslices, co
                                                       const uint8_t *__restrict__ st_mask, const double *__restrict__ X,
                                                       double *__restrict__ Y, i64 ld, i64 own, int b0,
                                                       const double *__restrict__ Bv, const double *__restrict__ dinv,
-                                                      double omega, double gamma, i64 per)
+                                                      double omega, double gamma, i64 per, double fs2, double fg)
 {
   constexpr int UPS = 4 / W;  // units per slice
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -183,6 +189,15 @@ __global__ __launch_bounds__(64 * W) void k_sell_mv8q(i64 nrows, i64 nslices, co
           o0 = bb.x - acc[q].x;
           o1 = bb.y - acc[q].y;
         }
+        else if (EPI == kFilt)
+        {
+          const double2 xk = *reinterpret_cast<const double2 *>(X + at);
+          const dv2 bb = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(Bv + at));
+          dv2 xo = dv2{0.0, 0.0};
+          if (fs2 != 0.0) xo = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(yr));
+          o0 = __builtin_fma(omega, acc[q].x, __builtin_fma(gamma, xk.x, __builtin_fma(fs2, xo.x, fg * bb.x)));
+          o1 = __builtin_fma(omega, acc[q].y, __builtin_fma(gamma, xk.y, __builtin_fma(fs2, xo.y, fg * bb.y)));
+        }
         else
         {
           const double2 xk = *reinterpret_cast<const double2 *>(X + at);
@@ -211,7 +226,8 @@ __global__ __launch_bounds__(256) void k_sell_mv8g(i64 nrows, i64 nslices, const
                                                    const i32 *__restrict__ st_delta, const uint8_t *__restrict__ st_mask,
                                                    const double *__restrict__ X, double *__restrict__ Y, i64 ld, i64 own,
                                                    int b0, const double *__restrict__ Bv,
-                                                   const double *__restrict__ dinv, double omega, double gamma, i64 per)
+                                                   const double *__restrict__ dinv, double omega, double gamma, i64 per,
+                                                   double fs2, double fg)
 {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int cp = lane & 3, rq = lane >> 2;
@@ -328,6 +344,15 @@ __global__ __launch_bounds__(256) void k_sell_mv8g(i64 nrows, i64 nslices, const
           o0 = omega * (xk.x + gd * (bb.x - o0) - xo.x) + xo.x;
           o1 = omega * (xk.y + gd * (bb.y - o1) - xo.y) + xo.y;
         }
+        if (EPI == kFilt)
+        {
+          const double2 xk = *reinterpret_cast<const double2 *>(X + at);
+          const dv2 bb = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(Bv + at));
+          dv2 xo = dv2{0.0, 0.0};
+          if (fs2 != 0.0) xo = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(yr));
+          o0 = __builtin_fma(omega, o0, __builtin_fma(gamma, xk.x, __builtin_fma(fs2, xo.x, fg * bb.x)));
+          o1 = __builtin_fma(omega, o1, __builtin_fma(gamma, xk.y, __builtin_fma(fs2, xo.y, fg * bb.y)));
+        }
         __builtin_nontemporal_store(dv2{o0, o1}, reinterpret_cast<dv2 *>(yr));
       }
     }
@@ -342,7 +367,7 @@ bool all_stencil(const eig_mat_s &A) { return A.n_stencil_slices == A.nslices &&
 namespace {
 template <int EPI>
 void sell_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, const double *Bv, const double *dinv,
-              double omega, double gamma, hipStream_t s)
+              double omega, double gamma, hipStream_t s, double fs2 = 0.0, double fg = 0.0)
 {
   EIG_CHECK(A.br == 1 && A.bc == 1, EIG_ERR_BLOCKSIZE,
             "matmul_sparse_tallskinny_blocked: only implemented for FieldMatrix<..,1,1>");
@@ -360,7 +385,7 @@ void sell_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, const doubl
 #define EIGMI_GRP(STV)                                                                                         \
   hipLaunchKernelGGL((k_sell_mv8g<1, 2, STV, EPI>), dim3((unsigned)gx), dim3(256), 0, s, A.nb_rows, A.nslices, \
                      A.slice_ptr, A.val, A.col, A.st_delta, A.st_mask, X, Y, A.window, A.own_offset, 0, Bv, dinv, \
-                     omega, gamma, per)
+                     omega, gamma, per, fs2, fg)
     if (st) EIGMI_GRP(true);
     else EIGMI_GRP(false);
 #undef EIGMI_GRP
@@ -390,7 +415,7 @@ void sell_mv8(const eig_mat_s &A, i64 m, const double *X, double *Y, const doubl
 #define EIGMI_QUAD(MBV, STV)                                                                                        \
   hipLaunchKernelGGL((k_sell_mv8q<MBV, 4, W, STV, EPI>), dim3((unsigned)gx), dim3(64 * W), 0, s, A.nb_rows, A.nslices, \
                      A.slice_ptr, A.val, A.col, A.st_delta, A.st_mask, X, Y, A.window, A.own_offset, b0, Bv, dinv,     \
-                     omega, gamma, per)
+                     omega, gamma, per, fs2, fg)
 #define EIGMI_QUAD_NB(STV)            \
   switch (nb)                         \
   {                                   \
@@ -465,6 +490,32 @@ void launch_cheb_step(const eig_mat_s &M, i64 m, const double *Xk, double *Xold,
   if (launch_box_cheb(M, m, Xk, Xold, B, dinv, omega, gamma, s)) return;
   if (launch_cheb_march(M, m, Xk, Xold, B, dinv, omega, gamma, s)) return;
   sell_mv8<kCheb>(M, m, Xk, Xold, B, dinv, omega, gamma, s);
+}
+
+int filt_step_launches(const eig_mat_s &A, i64 m)
+{
+  if (A.br == A.bc && A.br > 1) return m >= 8 ? 1 : 0;  // one k_spmm_blk_mv8_filt launch (grid.y)
+  if (box_spmm_applies(A, m)) return A.box_ctab ? 1 : (int)(m / 32);
+  return sell_mv8_launches(m);
+}
+
+void launch_filt_step(const eig_mat_s &A, i64 m, const double *Xk, double *Xold, const double *B, double s1,
+                      double s0, double s2, double g, hipStream_t s)
+{
+  EIG_CHECK(Xk != Xold && B != Xold, EIG_ERR_ARG, "filter step: the output buffer must be neither x_k nor b");
+  if (A.br == A.bc && A.br > 1)
+  {
+    // square blocks 2..4: the epilogue on the blocked product (k_mv8.hip)
+    launch_filt_step_blk(A, m, Xk, Xold, B, s1, s0, s2, g, s);
+    return;
+  }
+  EIG_CHECK(A.br == 1 && A.bc == 1, EIG_ERR_BLOCKSIZE, "filter step: 1x1 blocks or square blocks 2..4");
+  EIG_CHECK(!A.ctx->distributed() && A.R == 1 && A.nb_rows == A.nb_cols && A.window == A.nb_rows, EIG_ERR_SHAPE,
+            "filter step: square single-rank matrix required");
+  // row-class / box image (k_box.hip), else the SELL kernels; the general band march (k_spmm8_marchg) has
+  // no filter epilogue and its matrices take the SELL fallback
+  if (launch_box_filt(A, m, Xk, Xold, B, s1, s0, s2, g, s)) return;
+  sell_mv8<kFilt>(A, m, Xk, Xold, B, nullptr, s1, s0, s, s2, g);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -48,7 +48,11 @@ enum {
   kBoxResidCopy = 6,
   kBoxResidAcc = 7,
   kBoxStoreDot = 8,  // kBoxStore + the diagonal dots x_j . y_j of each column (row-class kernel only)
-  kBoxStoreDotGram = 9  // kBoxStoreDot + the window Gram y_w . y_c of the 8 columns (m = 8; reduce_dev.h)
+  kBoxStoreDotGram = 9,  // kBoxStoreDot + the window Gram y_w . y_c of the 8 columns (m = 8; reduce_dev.h)
+  // one Clenshaw step of the Chebyshev window filter (filter_host.h): out = s1 acc + s0 x_k + s2 x_old + g b
+  // with FMA as kBoxCheb, s1 / s0 in the omega / gamma slots and s2 / g beside them; x_old (Xold) null: not
+  // read (s2 x_old = 0); no D^-1 stream
+  kBoxFilt = 10
 };
 // kBoxStoreDot's reduction: dp[8 b + j] = sum_r X(r, 8b + j) Y(r, 8b + j), one deterministic grid sum
 // (workgroup partials in part, a ticket per column block) -- dot_products_diagonal_blocked fused into
@@ -59,6 +63,7 @@ struct BoxDot {
   unsigned *tick = nullptr;
   double *gram = nullptr;  // kBoxStoreDotGram: the 8 x 8 window Gram of Y (row-major, upper triangle)
   unsigned *zero_word = nullptr;  // kBoxStoreDotGram: zeroed by the last workgroup (the next MGS's barrier)
+  double fs2 = 0.0, fg = 0.0;     // kBoxFilt (k_boxc_mv8): the scalars s2 and g
 };
 constexpr int kBoxMaxNd = 15;  // offsets of the box-image kernel's LDS value tile (P1 Kuhn: 15, 7-point: 7)
 constexpr int kBoxClassMaxNd = 27;  // offsets of the row-class kernels (27: Galerkin coarse operators)
@@ -161,7 +166,7 @@ __global__ __launch_bounds__(kBoxThreads) void k_box_mv32(BoxGeom g, i64 ld, con
                                                           const double *__restrict__ Xold,
                                                           const double *__restrict__ Bv,
                                                           const double *__restrict__ dinv, double omega,
-                                                          double gamma)
+                                                          double gamma, double fs2, double fg)
 {
   // X of planes z-1, z, z+1 (tile + halo, 32 columns per row, 256-B rows; column c of an odd row
   // at c ^ 2: the 16-B reads of lanes on adjacent rows then fall on distinct banks), and the
@@ -254,8 +259,8 @@ __global__ __launch_bounds__(kBoxThreads) void k_box_mv32(BoxGeom g, i64 ld, con
     const double *br = Bv + (i64)blk * ld * 8 + r * 8 + c4;
 #pragma unroll
     for (int j = 0; j < 2; ++j) b2[j] = __builtin_nontemporal_load(reinterpret_cast<const dv2b *>(br) + j);
-    if (EPI != kBoxCheb) return;
-    gg = gamma * __builtin_nontemporal_load(dinv + r);
+    if (EPI != kBoxCheb && EPI != kBoxFilt) return;
+    if (EPI == kBoxCheb) gg = gamma * __builtin_nontemporal_load(dinv + r);
     if (!Xold) return;  // x_{k-1} = 0 (the first step from a zero start): not read
     const double *yr = Xold + (i64)blk * ld * 8 + r * 8 + c4;
 #pragma unroll
@@ -361,8 +366,18 @@ __global__ __launch_bounds__(kBoxThreads) void k_box_mv32(BoxGeom g, i64 ld, con
 #pragma unroll
         for (int j = 0; j < 2; ++j)
         {
-          const double o0 = omega * (xc[2 * j] + gd * (bb[j].x - acc[2 * j]) - xo[j].x) + xo[j].x;
-          const double o1 = omega * (xc[2 * j + 1] + gd * (bb[j].y - acc[2 * j + 1]) - xo[j].y) + xo[j].y;
+          double o0, o1;
+          if (EPI == kBoxFilt)
+          {
+            o0 = __builtin_fma(omega, acc[2 * j], __builtin_fma(gamma, xc[2 * j], __builtin_fma(fs2, xo[j].x, fg * bb[j].x)));
+            o1 = __builtin_fma(omega, acc[2 * j + 1],
+                               __builtin_fma(gamma, xc[2 * j + 1], __builtin_fma(fs2, xo[j].y, fg * bb[j].y)));
+          }
+          else
+          {
+            o0 = omega * (xc[2 * j] + gd * (bb[j].x - acc[2 * j]) - xo[j].x) + xo[j].x;
+            o1 = omega * (xc[2 * j + 1] + gd * (bb[j].y - acc[2 * j + 1]) - xo[j].y) + xo[j].y;
+          }
           __builtin_nontemporal_store(dv2b{o0, o1}, reinterpret_cast<dv2b *>(yr) + j);
         }
       }
@@ -406,7 +421,7 @@ __global__ __launch_bounds__(kPThreads, 4) void k_box_mv16p(BoxGeom g, i64 ld, i
                                                             const double *__restrict__ Xold,
                                                             const double *__restrict__ Bv,
                                                             const double *__restrict__ dinv, double omega,
-                                                            double gamma)
+                                                            double gamma, double fs2, double fg)
 {
   __shared__ __attribute__((aligned(16))) double slot[kBoxHY * kBoxHX][kPCols];
   __shared__ double atile[kBoxMaxNd][kBoxTX * kBoxTY];
@@ -512,8 +527,8 @@ __global__ __launch_bounds__(kPThreads, 4) void k_box_mv16p(BoxGeom g, i64 ld, i
     const double *br = Bv + (i64)blk * ld * 8 + r * 8 + c4;
 #pragma unroll
     for (int j = 0; j < 2; ++j) b2[j] = __builtin_nontemporal_load(reinterpret_cast<const dv2b *>(br) + j);
-    if (EPI != kBoxCheb) return;
-    gg = gamma * dinv[r];
+    if (EPI != kBoxCheb && EPI != kBoxFilt) return;
+    if (EPI == kBoxCheb) gg = gamma * dinv[r];
     if (!Xold) return;
     const double *yr = Xold + (i64)blk * ld * 8 + r * 8 + c4;
 #pragma unroll
@@ -612,14 +627,24 @@ __global__ __launch_bounds__(kPThreads, 4) void k_box_mv16p(BoxGeom g, i64 ld, i
 #pragma unroll
         for (int j = 0; j < 2; ++j)
         {
-          const double o0 = omega * (xr[2 * j] + gd * (bb[j].x - am[2 * j]) - xo[j].x) + xo[j].x;
-          const double o1 = omega * (xr[2 * j + 1] + gd * (bb[j].y - am[2 * j + 1]) - xo[j].y) + xo[j].y;
+          double o0, o1;
+          if (EPI == kBoxFilt)
+          {
+            o0 = __builtin_fma(omega, am[2 * j], __builtin_fma(gamma, xr[2 * j], __builtin_fma(fs2, xo[j].x, fg * bb[j].x)));
+            o1 = __builtin_fma(omega, am[2 * j + 1],
+                               __builtin_fma(gamma, xr[2 * j + 1], __builtin_fma(fs2, xo[j].y, fg * bb[j].y)));
+          }
+          else
+          {
+            o0 = omega * (xr[2 * j] + gd * (bb[j].x - am[2 * j]) - xo[j].x) + xo[j].x;
+            o1 = omega * (xr[2 * j + 1] + gd * (bb[j].y - am[2 * j + 1]) - xo[j].y) + xo[j].y;
+          }
           __builtin_nontemporal_store(dv2b{o0, o1}, reinterpret_cast<dv2b *>(yr) + j);
         }
       }
     }
     fetch_cheb(p, bb, xo, gd);
-    if (EPI == kBoxCheb)  // the own row's X on plane p, for its epilogue in iteration p + 1
+    if (EPI == kBoxCheb || EPI == kBoxFilt)  // the own row's X on plane p, for its epilogue in iteration p + 1
     {
       xc[0] = *reinterpret_cast<const dv2b *>(&slot[hrow][swz(hrow, blk * 8 + c4)]);
       xc[1] = *reinterpret_cast<const dv2b *>(&slot[hrow][swz(hrow, blk * 8 + c4 + 2)]);
@@ -726,6 +751,7 @@ __global__ __launch_bounds__(kCThreads, EPI == kBoxStoreDotGram ? 4 : 8) void k_
   const int x0 = (tile % g.ntx) * kCTX, y0 = (tile / g.ntx) * kCTY;
   const int z0 = seg * g.nz / g.nseg, z1 = (seg + 1) * g.nz / g.nseg;
   constexpr bool first = EPI == kBoxChebFirst || EPI == kBoxChebFirstAdd;
+  constexpr bool filt = EPI == kBoxFilt;
   constexpr bool cheb = EPI == kBoxCheb || first || EPI == kBoxChebSecond;
   constexpr bool plain = EPI == kBoxStore || EPI == kBoxStoreDot || EPI == kBoxStoreDotGram;  // Y = A X
   constexpr bool dot = EPI == kBoxStoreDot || EPI == kBoxStoreDotGram;
@@ -779,7 +805,7 @@ __global__ __launch_bounds__(kCThreads, EPI == kBoxStoreDotGram ? 4 : 8) void k_
       b2 = Bb[r * 4 + cp];  // (the plane just went through the ring: an L2 hit)
     else
       b2 = __builtin_nontemporal_load(Bb + r * 4 + cp);
-    if (EPI == kBoxCheb && Ob) x2 = __builtin_nontemporal_load(Ob + r * 4 + cp);  // (null: x_{k-1} = 0)
+    if ((EPI == kBoxCheb || filt) && Ob) x2 = __builtin_nontemporal_load(Ob + r * 4 + cp);  // (null: x_{k-1} = 0)
   };
   fetch(z0 - 1);
   store(z0 - 1);
@@ -822,7 +848,7 @@ __global__ __launch_bounds__(kCThreads, EPI == kBoxStoreDotGram ? 4 : 8) void k_
       // halo row, and +0 added to a sum that starts at +0 changes nothing -- the same sums as with
       // the mask.  LDS offsets are immediates off three per-plane slot bases.
       constexpr BoxShapeTab T = box_shape_tab(SHAPE);
-      constexpr int kGroup = cheb ? 2 : 4;  // (the Chebyshev step holds 4 more vectors)
+      constexpr int kGroup = cheb || filt ? 2 : 4;  // (the Chebyshev and filter steps hold 4 more vectors)
       // ring index (dv2b units) of the (-1, -1) neighbour in the three slots, made opaque to the
       // compiler: otherwise it hoists base + offset for every offset out of the plane loop (one
       // live VGPR per offset and slot, ~110 VGPRs: one workgroup per CU instead of two)
@@ -881,6 +907,13 @@ __global__ __launch_bounds__(kCThreads, EPI == kBoxStoreDotGram ? 4 : 8) void k_
           }
           Xs[r * 4 + cp] = v;
         }
+      }
+      else if constexpr (filt)
+      {
+        const dv2b xc = ring[s0][hrow][cp];
+        const double o0 = __builtin_fma(omega, acc.x, __builtin_fma(gamma, xc.x, __builtin_fma(bd.fs2, xo.x, bd.fg * bb.x)));
+        const double o1 = __builtin_fma(omega, acc.y, __builtin_fma(gamma, xc.y, __builtin_fma(bd.fs2, xo.y, bd.fg * bb.y)));
+        __builtin_nontemporal_store(dv2b{o0, o1}, Yb + r * 4 + cp);
       }
       else
       {
@@ -1159,7 +1192,7 @@ static bool launch_box(const eig_mat_s &A, i64 m, const double *X, double *Y, co
                        const double *dinv, double omega, double gamma, int epi, hipStream_t s, BoxDot bd = {})
 {
   if (m <= 0 || m % 8 != 0 || !box_prepare(A)) return false;
-  if (epi >= kBoxChebFirst && !A.box_ctab) return false;  // (row-class only)
+  if (epi >= kBoxChebFirst && epi != kBoxFilt && !A.box_ctab) return false;  // (row-class only)
   if ((epi == kBoxStoreDot || epi == kBoxStoreDotGram) && !A.box_ctab) return false;
   if (epi == kBoxStoreDotGram && m != 8) return false;
   // a rank's slab (A.ctx->distributed()): the product and the Chebyshev step only, the window's ghost
@@ -1246,6 +1279,9 @@ static bool launch_box(const eig_mat_s &A, i64 m, const double *X, double *Y, co
       else if (epi == kBoxStoreDotGram)
         hipLaunchKernelGGL((k_boxc_mv8<kBoxStoreDotGram, S>), grid, dim3(kCThreads), 0, s, g, A.window, ct, cm, X, Y,
                            (const double *)nullptr, (const double *)nullptr, 0.0, 0.0, bd);
+      else if (epi == kBoxFilt)
+        hipLaunchKernelGGL((k_boxc_mv8<kBoxFilt, S>), grid, dim3(kCThreads), 0, s, g, A.window, ct, cm, X, Y, Xold,
+                           Bv, omega, gamma, bd);
       else
         hipLaunchKernelGGL((k_boxc_mv8<kBoxStore, S>), grid, dim3(kCThreads), 0, s, g, A.window, ct, cm, X, Y,
                            (const double *)nullptr, (const double *)nullptr, 0.0, 0.0, bd);
@@ -1304,29 +1340,38 @@ static bool launch_box(const eig_mat_s &A, i64 m, const double *X, double *Y, co
         if (epi == kBoxCheb)
           hipLaunchKernelGGL((k_box_mv16p<kBoxCheb, S>), pgrid, dim3(kPThreads), 0, s, g, ld, items,
                              (const double *)A.box_val, m32, m8, X + off, Y + off, Xold ? Xold + off : nullptr,
-                             Bv + off, dinv, omega, gamma);
+                             Bv + off, dinv, omega, gamma, 0.0, 0.0);
+        else if (epi == kBoxFilt)
+          hipLaunchKernelGGL((k_box_mv16p<kBoxFilt, S>), pgrid, dim3(kPThreads), 0, s, g, ld, items,
+                             (const double *)A.box_val, m32, m8, X + off, Y + off, Xold ? Xold + off : nullptr,
+                             Bv + off, (const double *)nullptr, omega, gamma, bd.fs2, bd.fg);
         else if (epi == kBoxResid)
           hipLaunchKernelGGL((k_box_mv16p<kBoxResid, S>), pgrid, dim3(kPThreads), 0, s, g, ld, items,
                              (const double *)A.box_val, m32, m8, X + off, Y + off, (const double *)nullptr,
-                             Bv + off, (const double *)nullptr, 0.0, 0.0);
+                             Bv + off, (const double *)nullptr, 0.0, 0.0, 0.0, 0.0);
         else
           hipLaunchKernelGGL((k_box_mv16p<kBoxStore, S>), pgrid, dim3(kPThreads), 0, s, g, ld, items,
                              (const double *)A.box_val, m32, m8, X + off, Y + off, (const double *)nullptr,
-                             (const double *)nullptr, (const double *)nullptr, 0.0, 0.0);
+                             (const double *)nullptr, (const double *)nullptr, 0.0, 0.0, 0.0, 0.0);
         continue;
       }
       const dim3 grid((unsigned)(tiles * g.nseg));
       if (epi == kBoxCheb)
         hipLaunchKernelGGL((k_box_mv32<kBoxCheb, S>), grid, dim3(kBoxThreads), 0, s, g, ld, (const double *)A.box_val,
-                           m32, m8, X + off, Y + off, Xold ? Xold + off : nullptr, Bv + off, dinv, omega, gamma);
+                           m32, m8, X + off, Y + off, Xold ? Xold + off : nullptr, Bv + off, dinv, omega, gamma, 0.0,
+                           0.0);
+      else if (epi == kBoxFilt)
+        hipLaunchKernelGGL((k_box_mv32<kBoxFilt, S>), grid, dim3(kBoxThreads), 0, s, g, ld, (const double *)A.box_val,
+                           m32, m8, X + off, Y + off, Xold ? Xold + off : nullptr, Bv + off, (const double *)nullptr,
+                           omega, gamma, bd.fs2, bd.fg);
       else if (epi == kBoxResid)
         hipLaunchKernelGGL((k_box_mv32<kBoxResid, S>), grid, dim3(kBoxThreads), 0, s, g, ld, (const double *)A.box_val,
                            m32, m8, X + off, Y + off, (const double *)nullptr, Bv + off, (const double *)nullptr, 0.0,
-                           0.0);
+                           0.0, 0.0, 0.0);
       else
         hipLaunchKernelGGL((k_box_mv32<kBoxStore, S>), grid, dim3(kBoxThreads), 0, s, g, ld, (const double *)A.box_val,
                            m32, m8, X + off, Y + off, (const double *)nullptr, (const double *)nullptr,
-                           (const double *)nullptr, 0.0, 0.0);
+                           (const double *)nullptr, 0.0, 0.0, 0.0, 0.0);
     }
   };
   if (A.box_geomask && shape == kShape7 && A.sym_nd == 7)
@@ -1391,6 +1436,17 @@ bool launch_box_cheb(const eig_mat_s &M, i64 m, const double *Xk, double *Xold, 
 {
   EIG_CHECK(Xold || Xnew, EIG_ERR_ARG, "box Chebyshev step: x_{k-1} = 0 needs a separate output buffer");
   return launch_box(M, m, Xk, Xnew ? Xnew : Xold, Xold, B, dinv, omega, gamma, kBoxCheb, s);
+}
+
+// One step of the window filter, in place over Xold (read only when s2 != 0); one rank only.  False when the
+// matrix has no row-class image and (m % 32 != 0 or no box image): the caller takes the SELL kernels.
+bool launch_box_filt(const eig_mat_s &A, i64 m, const double *Xk, double *Xold, const double *B, double s1, double s0,
+                     double s2, double g, hipStream_t s)
+{
+  BoxDot bd;
+  bd.fs2 = s2;
+  bd.fg = g;
+  return launch_box(A, m, Xk, Xold, s2 != 0.0 ? Xold : nullptr, B, nullptr, s1, s0, kBoxFilt, s, bd);
 }
 
 // The first Chebyshev step from x_0 = 0, x_1 = gamma D^-1 B never stored: Y = x_2 straight from B

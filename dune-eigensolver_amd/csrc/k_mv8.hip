@@ -275,6 +275,65 @@ __global__ __launch_bounds__(256) void k_spmm_blk_mv8_cheb(i64 nbrows, i64 nslic
   }
 }
 
+// One Clenshaw step of the Chebyshev window filter (filter_host.h) fused into the blocked product: the same
+// image, lane mapping, slice walk and row sums as k_spmm_blk_mv8 (spmm_blk_row); then per scalar row and column
+// pair, with acc = (A x_k)_row,
+//     out = s1 acc + s0 x_k + s2 x_old + g b        (fused multiply-adds: tolerance-checked)
+// written in place over x_old (Xold: each lane reads its own rows before it stores them; s2 == 0, the filter's
+// first two steps, reads none); x_k is the gathered input Xk, never Xold.  b and x_old are read once
+// (nontemporal loads, nontemporal stores of the result); no D^-1 stream.  Every epilogue access is under the
+// store's guards (row < nbrows, b0 + q < nblk_total).
+template <int B, int MB>
+__global__ __launch_bounds__(256) void k_spmm_blk_mv8_filt(i64 nbrows, i64 nslices, const i64 *__restrict__ slice_ptr,
+                                                           const double *__restrict__ val,
+                                                           const i32 *__restrict__ col, const double *__restrict__ Xk,
+                                                           double *__restrict__ Xold, i64 n, int nblk_total,
+                                                           int xcd_map, const double *__restrict__ Bv, double s1,
+                                                           double s0, double s2, double g)
+{
+  const int wave = threadIdx.x >> 6, L = threadIdx.x & 63;
+  const int cp = L & 3;
+  const int ri = wave * 16 + (L >> 2);
+  const int b0 = blockIdx.y * MB;
+  const BlkSliceWalk w = blk_slice_walk(nslices, xcd_map);
+  for (i64 s = w.s0; s < w.s1; s += w.step)
+  {
+    double2 acc[MB][B];
+    spmm_blk_row<B, MB>(slice_ptr, val, col, Xk, n, nblk_total, b0, s, ri, cp, acc);
+    const i64 row = s * 64 + ri;
+    if (row < nbrows)
+    {
+#pragma unroll
+      for (int q = 0; q < MB; ++q)
+        if (b0 + q < nblk_total)
+        {
+          const i64 at = ((i64)(b0 + q) * n + row * B) * 8 + 2 * cp;
+          dv2 xk[B], bb[B], xo[B];
+#pragma unroll
+          for (int r = 0; r < B; ++r)
+          {
+            xk[r] = *reinterpret_cast<const dv2 *>(Xk + at + r * 8);
+            bb[r] = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(Bv + at + r * 8));
+            xo[r] = dv2{0.0, 0.0};
+          }
+          if (s2 != 0.0)
+          {
+#pragma unroll
+            for (int r = 0; r < B; ++r)
+              xo[r] = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(Xold + at + r * 8));
+          }
+#pragma unroll
+          for (int r = 0; r < B; ++r)
+          {
+            const double o0 = __builtin_fma(s1, acc[q][r].x, __builtin_fma(s0, xk[r].x, __builtin_fma(s2, xo[r].x, g * bb[r].x)));
+            const double o1 = __builtin_fma(s1, acc[q][r].y, __builtin_fma(s0, xk[r].y, __builtin_fma(s2, xo[r].y, g * bb[r].y)));
+            __builtin_nontemporal_store(dv2{o0, o1}, reinterpret_cast<dv2 *>(Xold + at + r * 8));
+          }
+        }
+    }
+  }
+}
+
 // R = Bv - A X: the residual epilogue on the blocked product (the multigrid's residual on blocks).  The same
 // image, lane mapping, slice walk and row sums as k_spmm_blk_mv8 (spmm_blk_row), then one subtraction per
 // element; every epilogue access is under the store's guards (row < nbrows, b0 + q < nblk_total).  R may be
@@ -393,6 +452,19 @@ static void launch_cheb_blk(const eig_mat_s &M, int nblk, const double *Xk, doub
                      M.slice_ptr, M.val, M.col, Xk, Xold, M.nb_rows * B, nblk, xcd ? 1 : 0, Bv, dinv, omega, gamma);
 }
 
+// The filter step on blocks: the Chebyshev step's grid and column blocks per workgroup.
+template <int B>
+static void launch_filt_blk(const eig_mat_s &A, int nblk, const double *Xk, double *Xold, const double *Bv, double s1,
+                            double s0, double s2, double g, hipStream_t s)
+{
+  constexpr int MB = spmm_blk_mb<B>();
+  const int gy = (nblk + MB - 1) / MB;
+  bool xcd;
+  const int gx = spmm_blk_grid_x(A, xcd);
+  hipLaunchKernelGGL((k_spmm_blk_mv8_filt<B, MB>), dim3(gx, gy), dim3(256), 0, s, A.nb_rows, A.nslices, A.slice_ptr,
+                     A.val, A.col, Xk, Xold, A.nb_rows * B, nblk, xcd ? 1 : 0, Bv, s1, s0, s2, g);
+}
+
 template <int B>
 static void launch_resid_blk(const eig_mat_s &A, int nblk, const double *X, const double *Bv, double *R, hipStream_t s)
 {
@@ -422,6 +494,22 @@ void launch_resid_blk_mv8(const eig_mat_s &A, i64 m, const double *X, const doub
     case 2: launch_resid_blk<2>(A, nblk, X, Bv, R, s); break;
     case 3: launch_resid_blk<3>(A, nblk, X, Bv, R, s); break;
     default: launch_resid_blk<4>(A, nblk, X, Bv, R, s); break;
+  }
+  EIG_HIP(hipGetLastError());
+}
+
+void launch_filt_step_blk(const eig_mat_s &A, i64 m, const double *Xk, double *Xold, const double *Bv, double s1,
+                          double s0, double s2, double g, hipStream_t s)
+{
+  const int nblk = (int)(m / 8);
+  check_blk_square(A, "blocked filter step");
+  EIG_CHECK(Xk != Xold && Bv != Xold, EIG_ERR_ARG, "blocked filter step: the output buffer must be neither x_k nor b");
+  if (nblk <= 0 || A.nb_rows <= 0) return;
+  switch (A.br)
+  {
+    case 2: launch_filt_blk<2>(A, nblk, Xk, Xold, Bv, s1, s0, s2, g, s); break;
+    case 3: launch_filt_blk<3>(A, nblk, Xk, Xold, Bv, s1, s0, s2, g, s); break;
+    default: launch_filt_blk<4>(A, nblk, Xk, Xold, Bv, s1, s0, s2, g, s); break;
   }
   EIG_HIP(hipGetLastError());
 }

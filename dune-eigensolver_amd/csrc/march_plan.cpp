@@ -458,6 +458,17 @@ std::string kernel_for(const eig_mat_s &A, int op)
         return op == 5 ? "k_box_mv32" : "k_box_mv32_cheb";
       }
       return kernel_for(A, op - 2);
+    case EIG_OP_FILT8:
+    case EIG_OP_FILT32:
+      // the filter step (launch_filt_step): blocked, row-class / box image, else SELL -- never the band march
+      if (!b1) return (A.br == A.bc && A.br >= 2 && A.br <= 4) ? "k_spmm_blk_mv8_filt" : "none";
+      if (box_prepare(A))
+      {
+        if (A.box_ctab) return "k_boxc_mv8_filt";
+        if (op == EIG_OP_FILT32) return box_cols(A) == 16 ? "k_box_mv16p_filt" : "k_box_mv32_filt";
+      }
+      if (A.nb_rows <= 0) return "none";
+      return op == EIG_OP_FILT8 ? "k_sell_mv8g_filt" : "k_sell_mv8q_filt";
     default:
       return "none";
   }

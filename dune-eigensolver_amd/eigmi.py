@@ -89,6 +89,12 @@ class LobpcgTiming(ctypes.Structure):
                 ("orth_rejected", ctypes.c_int64), ("orth_dev", ctypes.c_double)]
 
 
+class SliceTiming(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("total_ms", "filter_ms", "orth_ms", "rr_ms", "resid_ms")] + \
+               [(k, ctypes.c_int64) for k in ("iters", "degree", "filter_launches", "in_window", "saturated",
+                                              "cholqr_recomputed")]
+
+
 class Timing(ctypes.Structure):
     _fields_ = [("total_ms", ctypes.c_double), ("spmv_ms", ctypes.c_double), ("update_ms", ctypes.c_double),
                 ("comm_ms", ctypes.c_double), ("spmv_launches", ctypes.c_int64)]
@@ -228,6 +234,17 @@ SIGNATURES = {
     "eig_lobpcg_destroy": (_int, [_vp]),
     "eig_lobpcg_resid_mv8": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "eig_lobpcg_update_mv8": (_int, [_vp, _i64, _i64, _int, _vp, _vp]),
+    "eig_filter_degree": (_int, [_dbl, _dbl, _dbl, _dbl, _int, ctypes.POINTER(_int)]),
+    "eig_filter_coefs": (_int, [_dbl, _dbl, _dbl, _dbl, _int, _vp]),
+    "eig_filter_step_mv8": (_int, [_vp, _i64, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl]),
+    "eig_filter_mv8": (_int, [_vp, _i64, _dbl, _dbl, _dbl, _dbl, _int, _vp, _vp, _vp]),
+    "eig_spectrum_bounds": (_int, [_vp, _int, _u, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
+    "eig_filter_count": (_int, [_vp, _dbl, _dbl, _dbl, _dbl, _int, _int, _u, ctypes.POINTER(_dbl)]),
+    "eig_slice_create": (_int, [_vp, _dbl, _dbl, _dbl, _dbl, _int, _int, _vp, _u, ctypes.POINTER(_vp)]),
+    "eig_slice_step": (_int, [_vp, _int, _dbl, ctypes.POINTER(_int), ctypes.POINTER(_int),
+                              ctypes.POINTER(SliceTiming)]),
+    "eig_slice_ritz": (_int, [_vp, ctypes.POINTER(_int), _vp, _vp, _vp]),
+    "eig_slice_destroy": (_int, [_vp]),
     "eig_flops_orthonormalize": (_dbl, [_i64, _i64]),
     "eig_bytes_orthonormalize_blocked": (_dbl, [_i64, _i64, _int]),
     "eig_gen_nnzb": (_i64, [_int, _int]),
@@ -486,11 +503,12 @@ class Matrix:
         self.ctx.check(lib.eig_mat_get_info(self.h, ctypes.byref(info)))
         return info
 
-    OPS = {"spmv": 0, "k1": 1, "fused": 2, "spmm8": 3, "cheb8": 4, "spmm32": 5, "cheb32": 6}
+    OPS = {"spmv": 0, "k1": 1, "fused": 2, "spmm8": 3, "cheb8": 4, "spmm32": 5, "cheb32": 6, "filt8": 7, "filt32": 8}
 
     def kernel(self, op):
-        """Kernel family a whole-matrix launch of `op` ("spmv", "k1", "fused", "spmm8", "cheb8")
-        picks on this image now (eig_mat_kernel_info)."""
+        """Kernel family a whole-matrix launch of `op` ("spmv", "k1", "fused", "spmm8", "cheb8", ...,
+        "filt8" / "filt32": the filter step at m = 8 / m % 32 == 0) picks on this image now
+        (eig_mat_kernel_info)."""
         buf = ctypes.create_string_buffer(64)
         self.ctx.check(lib.eig_mat_kernel_info(self.h, self.OPS[op], buf, 64))
         return buf.value.decode()
@@ -1155,6 +1173,98 @@ class Lobpcg:
     def close(self):
         if self.h and self.K.h and self.K.ctx.h:
             lib.eig_lobpcg_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# --------------------------------------------------------------------------------------- spectrum slicing
+def _host_check(rc):
+    if rc != EIG_OK:
+        raise EigError(rc, lib.eig_last_error(None).decode())
+
+
+def filter_degree(a, b, lmin, lmax, degree=0):
+    """The degree a filter call with `degree` takes (0: the default rule; eig_filter_degree, host only)."""
+    d = _int(0)
+    _host_check(lib.eig_filter_degree(a, b, lmin, lmax, degree, ctypes.byref(d)))
+    return d.value
+
+
+def filter_coefs(a, b, lmin, lmax, degree=0):
+    """gamma_0 .. gamma_d of the Jackson-damped Chebyshev window filter (eig_filter_coefs, host only)."""
+    gam = np.zeros(filter_degree(a, b, lmin, lmax, degree) + 1)
+    _host_check(lib.eig_filter_coefs(a, b, lmin, lmax, degree, _np_ptr(gam)))
+    return gam
+
+
+def filter_step_mv8(A, m, Xk, Xold, B, s1, s0, s2, g):
+    """Xold <- s1 (A Xk) + s0 Xk + s2 Xold + g B in one fused launch (eig_filter_step_mv8); Xold is read only
+    when s2 != 0."""
+    A.ctx.check(lib.eig_filter_step_mv8(A.h, m, Xk.ptr, Xold.ptr, B.ptr, s1, s0, s2, g))
+
+
+def filter_mv8(A, m, a, b, lmin, lmax, degree, X, Y, work):
+    """Y = p(A) X, the window filter of [a, b]; work: one more n x m panel (eig_filter_mv8)."""
+    A.ctx.check(lib.eig_filter_mv8(A.h, m, a, b, lmin, lmax, degree, X.ptr, Y.ptr, work.ptr))
+
+
+def spectrum_bounds(A, steps=30, seed=123):
+    """(lmin, lmax) enclosing the spectrum of A from `steps` Lanczos steps (eig_spectrum_bounds)."""
+    lo, hi = _dbl(0.0), _dbl(0.0)
+    A.ctx.check(lib.eig_spectrum_bounds(A.h, steps, seed, ctypes.byref(lo), ctypes.byref(hi)))
+    return lo.value, hi.value
+
+
+def filter_count(A, a, b, lmin, lmax, degree=0, nvec=32, seed=123):
+    """Stochastic estimate of the number of eigenvalues of A in [a, b] (eig_filter_count)."""
+    est = _dbl(0.0)
+    A.ctx.check(lib.eig_filter_count(A.h, a, b, lmin, lmax, degree, nvec, seed, ctypes.byref(est)))
+    return est.value
+
+
+class Slice:
+    """eig_slice_t: every eigenpair of the symmetric A in [a, b] by Chebyshev-filtered subspace iteration,
+    see include/eigmi.h.  A: 1x1 blocks or square blocks b = 2..4 on one rank; [lmin, lmax] encloses the
+    spectrum (spectrum_bounds); degree = 0: the default rule.  X0: a DeviceArray holding the n x block start
+    block (MultiVector<double,8> layout), or None for the seeded random block."""
+
+    def __init__(self, A, a, b, lmin, lmax, block=32, degree=0, X0=None, seed=123):
+        self.A, self.block = A, block
+        self.h = None
+        h = _vp()
+        A.ctx.check(lib.eig_slice_create(A.h, a, b, lmin, lmax, block, degree, X0.ptr if X0 is not None else None,
+                                         seed, ctypes.byref(h)))
+        self.h = h
+        _track(self)
+
+    def step(self, max_iters, tol):
+        """-> (iterations done, converged, SliceTiming); tol = 0 forces max_iters iterations."""
+        it, conv, t = _int(0), _int(0), SliceTiming()
+        self.A.ctx.check(lib.eig_slice_step(self.h, max_iters, tol, ctypes.byref(it), ctypes.byref(conv),
+                                            ctypes.byref(t)))
+        return it.value, bool(conv.value), t
+
+    def ritz(self, want_evec=False, want_resid=True):
+        """The accepted pairs (theta in [a, b], ascending): (eval, evec or None, resid or None)."""
+        n = self.A.info.n
+        cnt = _int(0)
+        ev = np.zeros(self.block)
+        evec = np.zeros(self.block * n) if want_evec else None
+        res = np.zeros(self.block) if want_resid else None
+        self.A.ctx.check(lib.eig_slice_ritz(self.h, ctypes.byref(cnt), _np_ptr(ev),
+                                            _np_ptr(evec) if want_evec else None,
+                                            _np_ptr(res) if want_resid else None))
+        k = cnt.value
+        return ev[:k], (evec.reshape(self.block, n)[:k] if want_evec else None), (res[:k] if want_resid else None)
+
+    def close(self):
+        if self.h and self.A.h and self.A.ctx.h:
+            lib.eig_slice_destroy(self.h)
         self.h = None
 
     def __del__(self):

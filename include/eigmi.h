@@ -242,10 +242,12 @@ int eig_lanczos_kernel_info(eig_mat_t mat, int fused, char *name, int name_len, 
 /* Kernel family a whole-matrix launch of `op` picks on this matrix image (its creation flags
  * included): EIG_OP_SPMV (eig_mv), EIG_OP_LANCZOS_K1, EIG_OP_LANCZOS_FUSED,
  * EIG_OP_SPMM8 (eig_spmm_mv8, per 8-column block), EIG_OP_CHEB8 (eig_mass_solve_mv8's step).
+ * EIG_OP_FILT8 / EIG_OP_FILT32: eig_filter_step_mv8 at m = 8 / at m % 32 == 0 (blocks 2..4 included).
  * EIG_OP_CHEB8 / EIG_OP_CHEB32 describe 1x1 images only ("none" on blocks, although
  * eig_mass_solve_mv8 takes square blocks 2..4: its step there is k_spmm_blk_mv8_cheb). */
 enum { EIG_OP_SPMV = 0, EIG_OP_LANCZOS_K1 = 1, EIG_OP_LANCZOS_FUSED = 2, EIG_OP_SPMM8 = 3, EIG_OP_CHEB8 = 4,
-       EIG_OP_SPMM32 = 5, EIG_OP_CHEB32 = 6 /* m % 32 == 0: the 3-D box-stencil kernel where it applies */ };
+       EIG_OP_SPMM32 = 5, EIG_OP_CHEB32 = 6 /* m % 32 == 0: the 3-D box-stencil kernel where it applies */,
+       EIG_OP_FILT8 = 7, EIG_OP_FILT32 = 8 };
 int eig_mat_kernel_info(eig_mat_t mat, int op, char *name, int name_len);
 
 /* Measurement / tuning override of a launch parameter the library otherwise derives from the
@@ -831,6 +833,78 @@ int eig_lobpcg_destroy(eig_lobpcg_t ws);
 int eig_lobpcg_resid_mv8(eig_ctx_t ctx, int64_t n, int64_t m, const double *KX, const double *MX,
                          const double *theta_dev, double *R, double *sums_dev);
 int eig_lobpcg_update_mv8(eig_ctx_t ctx, int64_t n, int64_t m, int kb, double *S, const double *C_dev);
+
+/* ---------------------------------------------------------------- spectrum slicing */
+/* Every eigenpair of a symmetric A in a window [a, b] by Chebyshev-filtered subspace iteration: no solve and no
+ * factorisation, so the window may lie anywhere in the spectrum.  [lmin, lmax] must enclose the spectrum of A
+ * (eig_spectrum_bounds gives such bounds).  With A^ = (A - c I) / e, c = (lmax + lmin) / 2, e = (lmax - lmin) / 2,
+ * the filter is p(A^) for the Jackson-damped Chebyshev expansion p = sum_k gamma_k T_k (k = 0 .. degree) of the
+ * indicator of the mapped window; it is applied by Clenshaw in `degree` products, each with the recurrence fused
+ * into its epilogue (eig_filter_step_mv8).  A: 1x1 blocks or square blocks b = 2..4 (vectors then have
+ * n = nb_rows * b scalar rows), otherwise EIG_ERR_BLOCKSIZE; one rank (a distributed context: EIG_ERR_ARG); a
+ * rectangular matrix: EIG_ERR_SHAPE.  Multivectors are n x m in MultiVector<double,8> layout on the device.
+ *
+ * Filter arguments (EIG_ERR_ARG otherwise): finite bounds with lmin < lmax, a < b, [a, b] meeting [lmin, lmax]
+ * (the window is clamped into it), degree >= 2 or degree = 0 for the default: ceil(4 pi / w) - 2 clamped to
+ * [20, 2000], w = arccos a^ - arccos b^ the window's angular width. */
+/* Host only.  The degree a call with `degree` takes (degree itself, or the default for 0). */
+int eig_filter_degree(double a, double b, double lmin, double lmax, int degree, int *degree_out);
+/* Host only.  gamma_host[0 .. d] with d = the degree as eig_filter_degree reports it. */
+int eig_filter_coefs(double a, double b, double lmin, double lmax, int degree, double *gamma_host);
+/* One fused step, with acc = A Xk:  Xold <- s1 acc + s0 Xk + s2 Xold + g B  (fused multiply-adds; an entry A
+ * does not store never enters acc).  Xold is the output and must be neither Xk nor B; it is READ only when
+ * s2 != 0 -- with s2 == 0 (the first-step flavour: the filter's first two steps have no b_{k+2}) its contents
+ * are ignored, whatever they are.  (The output lives in Xold, so there is no Xold = NULL form.)  m % 8 == 0. */
+int eig_filter_step_mv8(eig_mat_t A, int64_t m, const double *Xk, double *Xold, const double *B, double s1,
+                        double s0, double s2, double g);
+/* Y = p(A) X.  work: one more n x m panel (the recurrence alternates between Y and work); X, Y, work distinct,
+ * X is not written. */
+int eig_filter_mv8(eig_mat_t A, int64_t m, double a, double b, double lmin, double lmax, int degree,
+                   const double *X, double *Y, double *work);
+/* `steps` Lanczos steps from the seeded start vector through the eig_lanczos_create workspace (two-kernel step;
+ * blocks 2..4 too), then lmin = theta_min - beta_k, lmax = theta_max + beta_k with theta the extreme eigenvalues
+ * of the k x k tridiagonal and beta_k the last residual norm: bounds that enclose the spectrum. */
+int eig_spectrum_bounds(eig_mat_t A, int steps, unsigned seed, double *lmin, double *lmax);
+/* (1 / nvec) sum_j z_j^T p(A) z_j over the nvec columns of eig_random_mv8(seed): the stochastic estimate of
+ * trace p(A), i.e. of the number of eigenvalues in [a, b] -- what `block` is sized by.  nvec % 8 == 0.  Its
+ * standard deviation is sqrt(2 sum_i p(lambda_i)^2 / nvec).  Allocates three n x nvec panels for the call. */
+int eig_filter_count(eig_mat_t A, double a, double b, double lmin, double lmax, int degree, int nvec,
+                     unsigned seed, double *estimate);
+/* The driver.  Per iteration: Y = p(A) X; CholQR2 of Y; H = Q^T A Q by a panel Gram; the host eigenproblem;
+ * X = Q S, A X = (A Q) S; R = A X - X diag(theta) with its column norms.  The pairs with theta in [a, b] are
+ * the accepted ones; a pair has converged at ||r_j|| <= tol max(|theta_j|, |a|, |b|) ||x_j||.  Memory: four
+ * n x block panels.  block in {8, 16, 24, 32}, else EIG_ERR_ARG; 4 * block > n: EIG_ERR_SHAPE.
+ * X0 (or NULL): the start block, n x block on the device, any basis of its span; NULL: mt19937(seed) normals
+ * in MultiVector fill order, as eig_random_mv8.  A start block without full rank: EIG_ERR_BREAKDOWN. */
+typedef struct eig_slice_s *eig_slice_t;
+typedef struct eig_slice_timing {
+  double total_ms;   /* device time of the iterations (events), the sum of the four below */
+  double filter_ms;  /* Y = p(A) X */
+  double orth_ms;    /* CholQR2 of Y */
+  double rr_ms;      /* A Q, H = Q^T A Q, the host eigenproblem, X = Q S and A X = (A Q) S */
+  double resid_ms;   /* the residual and its column sums (k_lobpcg_resid) */
+  int64_t iters;
+  int64_t degree;            /* the filter's degree (the default resolved) */
+  int64_t filter_launches;   /* filter step kernel launches of this call */
+  int64_t in_window;         /* Ritz values in [a, b] after the last iteration */
+  int64_t saturated;         /* 1 when all `block` Ritz values lie in [a, b]: the block cannot show that it found
+                                every eigenvalue of the window, and the caller must enlarge it */
+  int64_t cholqr_recomputed; /* (M = I: always 0; kept beside the other drivers' counters) */
+} eig_slice_timing;
+int eig_slice_create(eig_mat_t A, double a, double b, double lmin, double lmax, int block, int degree,
+                     const double *X0, unsigned seed, eig_slice_t *ws);
+/* Up to max_iters iterations, stopping when there is an accepted pair and every accepted pair has converged
+ * (tol = 0: exactly max_iters iterations; a workspace that already meets tol takes none).  An empty window
+ * never reports convergence.  iters_done, converged, timing: outputs, or NULL.  A non-positive CholQR2 pivot
+ * returns EIG_ERR_BREAKDOWN (the workspace can still be destroyed). */
+int eig_slice_step(eig_slice_t ws, int max_iters, double tol, int *iters_done, int *converged,
+                   eig_slice_timing *timing);
+/* The accepted pairs, theta ascending: *count of them (at most block: size the arrays for block entries);
+ * eval_host[count], evec_host: count unit vectors of n rows, resid_host[count] = ||A x - theta x||_2 from a fresh
+ * product (each or NULL).  With resid_host it overwrites two of the workspace's panels, which are scratch
+ * between eig_slice_step calls. */
+int eig_slice_ritz(eig_slice_t ws, int *count, double *eval_host, double *evec_host, double *resid_host);
+int eig_slice_destroy(eig_slice_t ws);
 
 /* a14: the reference's analytic GS models (kernels_cpp.hh:98-116, :157-175). */
 double eig_flops_orthonormalize(int64_t n, int64_t m);

@@ -727,6 +727,68 @@ class Lobpcg {
   eig_lobpcg_t h_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------------ spectrum slicing
+// Every eigenpair of the symmetric A in [a, b] by Chebyshev-filtered subspace iteration (eig_slice_*,
+// include/eigmi.h); [lmin, lmax] encloses the spectrum (spectrum_bounds), degree = 0 takes the default rule.
+// The matrix must outlive the solver.
+inline void spectrum_bounds(const Matrix &A, double &lmin, double &lmax, int steps = 30, unsigned seed = 123)
+{
+  check(eig_spectrum_bounds(A.get(), steps, seed, &lmin, &lmax), A.ctx());
+}
+// the stochastic estimate of the number of eigenvalues in [a, b]: what `block` is sized by
+inline double filter_count(const Matrix &A, double a, double b, double lmin, double lmax, int degree = 0,
+                           int nvec = 32, unsigned seed = 123)
+{
+  double est = 0.0;
+  check(eig_filter_count(A.get(), a, b, lmin, lmax, degree, nvec, seed, &est), A.ctx());
+  return est;
+}
+
+class Slice {
+ public:
+  Slice(const Matrix &A, double a, double b, double lmin, double lmax, int block, int degree = 0,
+        unsigned seed = 123, const double *X0_device = nullptr)
+      : ctx_(A.ctx()), n_((std::size_t)A.info().n), block_(block)
+  {
+    check(eig_slice_create(A.get(), a, b, lmin, lmax, block, degree, X0_device, seed, &h_), ctx_);
+  }
+  Slice(const Slice &) = delete;
+  Slice &operator=(const Slice &) = delete;
+  ~Slice() { eig_slice_destroy(h_); }
+  // up to max_iters iterations; true when there is a pair in [a, b] and every such pair holds
+  // ||A x - theta x|| <= tol max(|theta|, |a|, |b|) ||x||.  timing->saturated: the block must be enlarged
+  bool step(int max_iters, double tol, int *iters_done = nullptr, eig_slice_timing *timing = nullptr)
+  {
+    int conv = 0;
+    check(eig_slice_step(h_, max_iters, tol, iters_done, &conv, timing), ctx_);
+    return conv != 0;
+  }
+  // the pairs in [a, b], ascending: values, vectors (count x n, row per vector; may be null) and true
+  // residuals (may be null); returns their number
+  int ritz(std::vector<double> &lambda, std::vector<double> *vectors = nullptr,
+           std::vector<double> *residuals = nullptr)
+  {
+    int count = 0;
+    lambda.resize(block_);
+    if (vectors) vectors->resize((std::size_t)block_ * n_);
+    if (residuals) residuals->resize(block_);
+    check(eig_slice_ritz(h_, &count, lambda.data(), vectors ? vectors->data() : nullptr,
+                         residuals ? residuals->data() : nullptr),
+          ctx_);
+    lambda.resize(count);
+    if (vectors) vectors->resize((std::size_t)count * n_);
+    if (residuals) residuals->resize(count);
+    return count;
+  }
+  eig_slice_t get() const { return h_; }
+
+ private:
+  eig_ctx_t ctx_;
+  std::size_t n_;
+  int block_;
+  eig_slice_t h_ = nullptr;
+};
+
 }  // namespace eigmi
 
 #endif  // EIGMI_HH

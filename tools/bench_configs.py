@@ -27,6 +27,11 @@
       residual per cycle, the transfers' algorithmic bytes, and LOBPCG block 32 with one AMG V-cycle against
       Chebyshev-Jacobi degree 4; amg_stats turns a kernel trace of that run into one line per transfer kernel
       and level
+  SLICE  the Chebyshev window filter's fused step (eig_filter_step_mv8's kernels) beside the Chebyshev-Jacobi
+      step of the mass solve in one process on the same image, alternated: 128^3 row-class m = 8, 256^3
+      variable-coefficient box image m = 32, the `general` SELL matrix 128^3 m = 32, C3 blocks m = 8 and 32;
+      one outer iteration's split at 256^3 x 32; and a full run on kind 8 at 128^3 (a window of about 10
+      eigenvalues sized with eig_filter_count, iterations to tol 1e-8).  EIGMI_SLICE_CASES picks a subset
 
 One JSON line per measurement; algorithmic bytes per SURVEY 8(d); peak 8 TB/s.
 """
@@ -928,9 +933,147 @@ def amg_stats(path, m):
                  median_us=round(float(np.median(t)), 2), min_us=round(min(t), 2), max_us=round(max(t), 2))
 
 
+def slice_step_pair(ctx, M, m, cfg, image_bytes, dinv_bytes, window):
+    """The filter step and the Chebyshev-Jacobi step on M at m columns, each from the difference of two
+    degrees (the first steps and the per-call setup cancel), alternated three times; medians.  Both degrees
+    keep the device busy for milliseconds: at degree 4 eig_mass_solve_mv8's host setup (its buffers) outlasts
+    the kernels at 128^3 x 8, and the difference then understates the step (52 us against the trace's 87)."""
+    n = M.info.n
+    a, b, lo, hi = window
+    X, Y, W = ctx.zeros(n * m), ctx.zeros(n * m), ctx.zeros(n * m)
+    ctx.check(eigmi.lib.eig_fill_normal(ctx.h, n * m, 5, X.ptr))
+    d0, d1 = 24, 64
+
+    def cheb(d):
+        eigmi.mass_solve_mv8(M, m, d, X, Y)
+        ctx.sync()
+
+    def filt(d):
+        eigmi.filter_mv8(M, m, a, b, lo, hi, d, X, Y, W)
+        ctx.sync()
+    for f in (cheb, filt):
+        f(d0)
+        f(d1)
+    tc, tf = [], []
+    for _ in range(3):
+        tc.append((wall(lambda: cheb(d1), 2)[0] - wall(lambda: cheb(d0), 2)[0]) / (d1 - d0))
+        tf.append((wall(lambda: filt(d1), 2)[0] - wall(lambda: filt(d0), 2)[0]) / (d1 - d0))
+    tc, tf = float(np.median(tc)), float(np.median(tf))
+    vec = 32 * m * n  # per row and column: 8 B gather, 8 B B, 16 B in place
+    emit(config=cfg, m=m, op="Chebyshev step", kernel=M.kernel("cheb32" if m % 32 == 0 else "cheb8"),
+         us=round(tc * 1e6, 1), bytes=vec + image_bytes + dinv_bytes,
+         frac=round((vec + image_bytes + dinv_bytes) / tc / 1e9 / PEAK, 4))
+    emit(config=cfg, m=m, op="filter step", kernel=M.kernel("filt32" if m % 32 == 0 else "filt8"),
+         us=round(tf * 1e6, 1), bytes=vec + image_bytes, frac=round((vec + image_bytes) / tf / 1e9 / PEAK, 4),
+         vs_cheb=round(tf / tc, 4))
+    for d in (X, Y, W):
+        d.free()
+
+
+def slice_stats(path):
+    """The Chebyshev and filter step kernels in a rocprofv3 --kernel-trace of the slice task: per kernel instance
+    and grid the launches, median, minimum and maximum (the blocked kernels' m = 8 and m = 32 launches share a
+    grid: their split is in the step pairs' own lines)."""
+    import csv
+    runs = {}
+    for r in csv.DictReader(open(path)):
+        name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "").replace("eigmi::", "")
+        if any(k in name for k in ("k_boxc_mv8", "k_box_mv32", "k_box_mv16p", "k_sell_mv8", "k_spmm_blk_mv8_cheb",
+                                   "k_spmm_blk_mv8_filt")):
+            key = (name, int(r["Grid_Size_X"]), int(r["Grid_Size_Y"]))
+            runs.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for (name, gx, gy), t in sorted(runs.items()):
+        emit(kernel=name, grid_threads=[gx, gy], calls=len(t), median_us=round(float(np.median(t)), 2),
+             min_us=round(min(t), 2), max_us=round(max(t), 2))
+
+
+def slice(ctx):
+    cases = os.environ.get("EIGMI_SLICE_CASES", "class,general,c3,box,run").split(",")
+    win = (1.0, 1.5, 0.0, 13.0)  # (the step's time does not depend on the window)
+    if "class" in cases:
+        r, c, v = eigmi.gen_matrix(eigmi.GEN_POISSON3D, 128)
+        M = eigmi.Matrix.from_bcsr(ctx, r, c, v)
+        slice_step_pair(ctx, M, 8, "7-pt Poisson 128^3, row-class image", 0, 0, win)
+        M.close()
+    if "general" in cases:
+        r, c, v = eigmi.gen_matrix(eigmi.GEN_POISSON3D, 128)
+        r, c, v = eigmi.scrambled_rcm(r, c, v, 123)
+        M = eigmi.Matrix.from_bcsr(ctx, r, c, v)
+        n, nnz = M.info.n, int(r[-1])
+        slice_step_pair(ctx, M, 32, "general (scrambled + RCM) Poisson 128^3, SELL", 12 * nnz + 4 * (n + 1), 8 * n, win)
+        M.close()
+    if "c3" in cases:
+        N = int(os.environ.get("EIGMI_C3_N", "64"))
+        r, c, v = eigmi.gen_matrix(eigmi.GEN_Q1ELAST3D, N)
+        M = eigmi.Matrix.from_bcsr(ctx, r, c, v, 3, 3)
+        nb, nnzb = r.size - 1, int(r[-1])
+        for m in (8, 32):
+            slice_step_pair(ctx, M, m, f"C3 Q1 elasticity {N}^3 3x3 BCSR", 76 * nnzb + 4 * (nb + 1), 8 * M.info.n, win)
+        M.close()
+    if "box" in cases:
+        N = int(os.environ.get("EIGMI_SLICE_N", "256"))
+        r, c, v = eigmi.gen_matrix(eigmi.GEN_VARCOEF3D, N)
+        M = eigmi.Matrix.from_bcsr(ctx, r, c, v)
+        del r, c, v
+        info = M.info
+        n = info.n
+        img = (8 * info.sym_offsets + info.sym_mask_bytes) * n
+        slice_step_pair(ctx, M, 32, f"7-pt variable coefficients {N}^3, box image", img, 8 * n, win)
+        # one outer iteration at block 32 (degree 40: the split, not a solve)
+        sl = eigmi.Slice(M, 1.0, 1.5, 0.0, 13.0, block=32, degree=40, seed=123)
+        sl.step(1, 0.0)
+        it, _, t = sl.step(2, 0.0)
+        emit(config=f"7-pt variable coefficients {N}^3, box image", op="slice iteration, block 32, degree 40",
+             kernel=M.kernel("filt32"), ms_per_iter=round(t.total_ms / it, 2), filter_ms=round(t.filter_ms / it, 2),
+             orth_ms=round(t.orth_ms / it, 2), rr_ms=round(t.rr_ms / it, 2), resid_ms=round(t.resid_ms / it, 2),
+             filter_us_per_step=round(t.filter_ms / it / 40 * 1e3, 1),
+             filter_frac=round((32 * 32 * n + img) / (t.filter_ms / it / 40 * 1e-3) / 1e9 / PEAK, 4))
+        sl.close()
+        M.close()
+    if "run" in cases:
+        # a full run: kind 8 at 128^3, SPD so lmin = 0, lmax from 30 Lanczos steps; the window starts above the
+        # lowest eigenvalues and is widened until eig_filter_count sees about 10 eigenvalues
+        N = int(os.environ.get("EIGMI_SLICE_RUN_N", "128"))
+        r, c, v = eigmi.gen_matrix(eigmi.GEN_VARCOEF3D, N)
+        M = eigmi.Matrix.from_bcsr(ctx, r, c, v)
+        del r, c, v
+        t0 = time.perf_counter()
+        _, hi = eigmi.spectrum_bounds(M, 30, 123)
+        bounds_s = time.perf_counter() - t0
+        h2 = (np.pi / (N + 1)) ** 2
+        a, b = 7.0 * h2, 9.0 * h2
+        counts = []
+        t0 = time.perf_counter()
+        for _ in range(8):
+            est = eigmi.filter_count(M, a, b, 0.0, hi, 0, 32, 7)
+            counts.append([round(b / h2, 2), round(est, 2)])
+            if est >= 9.0:
+                break
+            b += 0.75 * h2
+        count_s = time.perf_counter() - t0
+        block = 24
+        degree = eigmi.filter_degree(a, b, 0.0, hi, 0)
+        sl = eigmi.Slice(M, a, b, 0.0, hi, block=block, degree=0, seed=123)
+        t0 = time.perf_counter()
+        it, conv, t = sl.step(30, 1e-8)
+        solve_s = time.perf_counter() - t0
+        ev, _, res = sl.ritz()
+        emit(config=f"7-pt variable coefficients {N}^3", op="slice run, tol 1e-8", window=[a, b], lmax=hi,
+             count_sweep=counts, count_s=round(count_s, 2), bounds_s=round(bounds_s, 3), block=block, degree=degree,
+             kernel=M.kernel("filt8"), iters=it, converged=bool(conv), found=int(ev.size), saturated=int(t.saturated),
+             solve_s=round(solve_s, 3), filter_ms=round(t.filter_ms, 1), orth_ms=round(t.orth_ms, 1),
+             rr_ms=round(t.rr_ms, 1), resid_ms=round(t.resid_ms, 1), max_resid=float(res.max()) if ev.size else None,
+             eigenvalues_over_h2=[round(float(x / h2), 4) for x in ev])
+        sl.close()
+        M.close()
+
+
 if __name__ == "__main__":
     if sys.argv[1:2] == ["mgblk_stats"]:
         mgblk_stats(sys.argv[2], sys.argv[3])
+        sys.exit(0)
+    if sys.argv[1:2] == ["slice_stats"]:
+        slice_stats(sys.argv[2])
         sys.exit(0)
     if sys.argv[1:2] == ["amg_stats"]:
         amg_stats(sys.argv[2], sys.argv[3])

@@ -25,6 +25,9 @@
 #                        with one V-cycle vs Chebyshev degree 4; then the same under a kernel trace -> mgblk.jsonl, mgblk_kernels.jsonl
 #   amg                  smoothed-aggregation AMG on the general (scrambled + RCM) Poisson 128^3: setup, V-cycle beside the
 #                        geometric one, LOBPCG vs Chebyshev degree 4; then a kernel trace per width -> amg.jsonl, amg_kernels.jsonl
+#   slice                the window filter's step beside the Chebyshev step (row-class 128^3, box image 256^3, general SELL
+#                        128^3, C3 blocks), one slice iteration's split at 256^3 x 32 and a full run at 128^3; then the
+#                        step pairs under a kernel trace -> slice.jsonl, slice_kernels.jsonl, slice_trace/
 #   latency              fused step vs eig_mv across sizes and slabs, plane-run counts  -> latency.jsonl
 #   marchcopy            the march streams alone (tools/march_copy.hip)       -> march_copy.jsonl
 #   prefetch             geometric march prefetch variants x plane runs (256^3, 128^3, slab) -> latency.jsonl
@@ -140,6 +143,12 @@ run_task() {
           python3 tools/bench_configs.py mgblk > "$O/mgblkt$m.jsonl" 2> "$O/mgblkt$m.err" || return 1
         python3 tools/bench_configs.py mgblk_stats "$(find "$O/mgblk_trace$m" -name '*kernel_trace.csv' | head -1)" $m >> "$O/mgblk_kernels.jsonl" || return 1
       done ;;
+    slice)
+      prof_env
+      timeout -k 10 900 python -u tools/bench_configs.py slice > "$O/slice.jsonl" 2> "$O/slice.err" || return 1
+      EIGMI_SLICE_CASES=class,general,c3 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/slice_trace" -o trace -- \
+        python3 tools/bench_configs.py slice > "$O/slicet.jsonl" 2> "$O/slicet.err" || return 1
+      python3 tools/bench_configs.py slice_stats "$(find "$O/slice_trace" -name '*kernel_trace.csv' | head -1)" > "$O/slice_kernels.jsonl" ;;
     amg)
       # plain run for the wall-clock numbers, then a kernel trace per width for the transfer kernels' own times
       # (k_amg_restrict / k_amg_prolong_add beside k_mg_restrict / k_mg_prolong_add in one process)
