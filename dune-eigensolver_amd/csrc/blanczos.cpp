@@ -12,13 +12,15 @@
 // Square blocks b = 2..4 (one rank): every vector has n = nb_rows * b scalar rows, the products are
 // k_spmm_blk_mv8, the Chebyshev step k_spmm_blk_mv8_cheb (k_mv8.hip) with point Jacobi on the scalar
 // diagonal of the diagonal blocks (k_diag_inv_blk); panels, CholQR2 and k_cheb_init see scalar rows only.
+// This file holds the workspace and its create / step / tmatrix / ritz / destroy; the Chebyshev solve, CholQR2
+// and the halo exchange of a block are subspace.h's, the block tridiagonal and the Ritz ordering subspace_host.h's.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <random>
 #include <vector>
 
-#include "internal.h"
+#include "subspace.h"
 
 using namespace eigmi;
 
@@ -45,207 +47,20 @@ struct eig_blanczos_s {
   std::vector<double> A, B;              // host: A_j (b x b), B_{j+1} (b x b, upper) per step
   ~eig_blanczos_s()
   {
-    delete V;
-    delete W;
-    delete Xa;
-    delete Xb;
-    delete Xc;
-    delete MZ;
-    delete dinv;
-    delete small;
-    delete chol;
+    for (DevBuf *d : {V, W, Xa, Xb, Xc, MZ, dinv, small, chol}) delete d;
   }
 };
 
 namespace {
 // the matrix whose diagonal / Chebyshev solve the operator uses: M (M^-1 K) or Ks (shift-invert)
 eig_mat_s &solve_mat(eig_blanczos_s &w) { return w.si ? *w.Ks : *w.M; }
-}  // namespace
 
-namespace {
-
-// Exchange the ghost rows of every column block of a window-layout multivector.
-void halo_mv(const eig_mat_s &A, double *X, i64 m, hipStream_t s)
-{
-  if (!A.ctx->distributed()) return;
-  for (i64 c = 0; c < m / 8; ++c) halo_exchange(A, X + c * A.window * 8, s, nullptr, 8);
-}
-
-// Chebyshev-Jacobi semi-iteration (Golub-Varga three-term form) for M X = Bv, `degree` steps on
-// the spectrum bounds [lmin, lmax] of diag(M)^-1 M: x_1 = gamma D^-1 b, then degree - 1 fused
-// steps  x_{k+1} = omega_{k+1} (x_k + gamma D^-1 (b - M x_k) - x_{k-1}) + x_{k-1}.  Returns the
-// buffer (Xa, Xb or Xc) that holds x_degree.  Error in the D-norm <= 2 rho^degree,
-// rho = (sqrt(kappa) - 1) / (sqrt(kappa) + 1), kappa = lmax / lmin.
-// Xc (optional third buffer): on the box kernel x_{k+1} goes to a buffer of its own instead of over
-// the x_{k-1} it reads (interleaved A/B at 256^3: 4.23 vs 4.28 ms per launch; box-to-box spread of
-// the same launch is 4.2-4.8 ms).
-}  // namespace
-
-namespace eigmi {
-double *cheb_solve(eig_mat_s &M, i64 m, int degree, double lmin, double lmax, const double *Bv, const double *dinv,
-                   double *Xa, double *Xb, double *Xc, hipStream_t s)
-{
-  // scalar rows; ld and own are scalar units already.  Square blocks 2..4 (one rank) take the in-place
-  // two-buffer branch below: the box kernels are 1x1 images
-  const bool blocked = M.br > 1 || M.bc > 1;
-  const i64 n = M.nb_rows * M.br, ld = M.window, own = M.own_offset;
-  const double gamma = 2.0 / (lmin + lmax), mu = (lmax - lmin) / (lmax + lmin);
-  double omega = 1.0 / (1.0 - 0.5 * mu * mu);  // omega_1
-  // Row-class image (one rank): x_1 = gamma D^-1 b is never stored -- the first step forms it while
-  // b's planes enter the LDS ring (x_2 straight from b), the second forms x_{k-1} = x_1 from the
-  // row's b.  Same arithmetic as the k_cheb_init + box-step chain below.
-  if (degree >= 2 && Xc && !blocked && !M.ctx->distributed() && launch_box_cheb_first(M, m, Bv, omega, gamma, Xa, s))
-  {
-    if (degree == 2) return Xa;
-    omega = 1.0 / (1.0 - 0.25 * mu * mu * omega);
-    EIG_CHECK(launch_box_cheb_second(M, m, Xa, Bv, omega, gamma, Xc, s), EIG_ERR_ARG,
-              "Chebyshev: second row-class step refused");
-    double *x2 = Xa;
-    Xa = Xc;  // x_3
-    Xc = Xb;
-    Xb = x2;
-    for (int k = 3; k < degree; ++k)
-    {
-      omega = 1.0 / (1.0 - 0.25 * mu * mu * omega);
-      launch_box_cheb(M, m, Xa, Xb, Bv, dinv, omega, gamma, s, Xc);  // Xc = x_{k+1}
-      double *t = Xb;
-      Xb = Xa;
-      Xa = Xc;
-      Xc = t;
-    }
-    return Xa;
-  }
-  launch_cheb_init(n, ld, own, m, Bv, dinv, gamma, Xa, s);
-  if (degree <= 1) return Xa;
-  const bool oop = Xc && !blocked && m % 32 == 0 && box_prepare(M);
-  // x_0 = 0: the box kernel (a third output buffer) takes it as "not read"; the in-place kernels
-  // read a cleared buffer
-  if (!oop) EIG_HIP(hipMemsetAsync(Xb, 0, (size_t)ld * m * sizeof(double), s));
-  for (int k = 1; k < degree; ++k)
-  {
-    if (k > 1) omega = 1.0 / (1.0 - 0.25 * mu * mu * omega);
-    halo_mv(M, Xa, m, s);
-    if (oop)
-    {
-      launch_box_cheb(M, m, Xa, k == 1 ? nullptr : Xb, Bv, dinv, omega, gamma, s, Xc);  // Xc = x_{k+1}
-      double *t = Xb;
-      Xb = Xa;
-      Xa = Xc;
-      Xc = t;
-    }
-    else
-    {
-      launch_cheb_step(M, m, Xa, Xb, Bv, dinv, omega, gamma, s);
-      std::swap(Xa, Xb);
-    }
-  }
-  return Xa;
-}
-}  // namespace eigmi
-
-namespace {
-double *dptr(DevBuf *b) { return b->d(); }
-
-// R0 diagonal spread beyond which CholQR2's second pass recomputes M Z instead of reusing (M Z) R0^-1
-constexpr double kCholQrReuseCond = 1e4;
-}  // namespace
-
-namespace eigmi {
-// CholQR2 in the M-inner product (internal.h CholQr2), shared by block Lanczos and LOBPCG.
-bool mcholqr2_mv(const CholQr2 &q, double *Z, double *Vdst, std::vector<double> &Rtot, long long &recomputed)
-{
-  eig_ctx_t ctx = q.ctx;
-  hipStream_t s = ctx->stream;
-  const int b = q.b;
-  const i64 n = q.n, ld = q.ld, own = q.own;
-  // M = I: M Z is Z itself, nothing to form or to carry
-  double *MZ = q.M ? q.MZ : Z;
-  double *Gd = q.small;
-  double *Sd = Gd + (size_t)b * b;
-  double *Rd = q.chol, *Rt = Rd + (size_t)b * b;
-  int *flag = reinterpret_cast<int *>(Rt + (size_t)b * b);
-  EIG_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
-  if (q.M)
-  {
-    halo_mv(*q.M, Z, b, s);
-    launch_spmm_mv8(*q.M, b, Z, MZ, s);
-  }
-  launch_panel_gram(ctx, n, ld, b, b, Z + own * 8, MZ + own * 8, Gd, s);
-  allreduce_sum(ctx, Gd, (i64)b * b, s);
-  launch_chol_small(b, 0, Gd, Rd, Sd, Rt, flag, s);  // Sd = R0^-1, Rt = R0
-  // The second pass may reuse M Z updated by the same factor (row-local: M (Z R0^-1) = (M Z) R0^-1 up
-  // to rounding) instead of a second M SpMM -- but that rounding gap is ~eps cond(Z), so for an
-  // ill-conditioned block the second pass would no longer restore M-orthonormality to ~eps (CholQR2's
-  // guarantee).  R0's diagonal decides (one small read-back): beyond kCholQrReuseCond the second pass
-  // recomputes M (Z R0^-1).
-  std::vector<double> r0((size_t)b * b);
-  EIG_HIP(hipMemcpyAsync(r0.data(), Rd, r0.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  EIG_HIP(hipStreamSynchronize(s));
-  double dmax = 0.0, dmin = HUGE_VAL;
-  for (int i = 0; i < b; ++i)
-  {
-    const double d = std::fabs(r0[(size_t)i * b + i]);
-    dmax = std::max(dmax, d);
-    dmin = std::min(dmin, d);
-  }
-  const bool reuse = dmin > 0.0 && dmax <= kCholQrReuseCond * dmin;
-  recomputed += !reuse && q.M;
-  if (reuse && b == 32 && q.M && !q.finish_mz)
-  {
-    // Z <- Z R0^-1 and the second pass's Gram (Z R0^-1)^T (M Z R0^-1) in one pass over Z and M Z
-    // (k_cholqr_fold): M Z R0^-1 is never stored, Z R0^-1 is not read back
-    launch_cholqr_fold(ctx, n, ld, Z + own * 8, MZ + own * 8, Sd, Gd, s);
-  }
-  else
-  {
-    launch_panel_update(n, ld, ld, b, b, Z + own * 8, Sd, 1.0, 0.0, Z + own * 8, s);
-    if (q.M)
-    {
-      if (reuse)
-        launch_panel_update(n, ld, ld, b, b, MZ + own * 8, Sd, 1.0, 0.0, MZ + own * 8, s);
-      else
-      {
-        halo_mv(*q.M, Z, b, s);
-        launch_spmm_mv8(*q.M, b, Z, MZ, s);
-      }
-    }
-    launch_panel_gram(ctx, n, ld, b, b, Z + own * 8, MZ + own * 8, Gd, s);
-  }
-  allreduce_sum(ctx, Gd, (i64)b * b, s);
-  launch_chol_small(b, 1, Gd, Rd, Sd, Rt, flag, s);  // Sd = R1^-1, Rt <- R1 R0
-  launch_panel_update(n, ld, ld, b, b, Z + own * 8, Sd, 1.0, 0.0, Vdst + own * 8, s);
-  // the caller carries M Vdst: the same factor on M Z (row-local, as above)
-  if (q.finish_mz && q.M) launch_panel_update(n, ld, ld, b, b, MZ + own * 8, Sd, 1.0, 0.0, MZ + own * 8, s);
-  Rtot.assign((size_t)b * b, 0.0);
-  int hflag = 0;
-  EIG_HIP(hipMemcpyAsync(Rtot.data(), Rt, Rtot.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  EIG_HIP(hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, s));
-  EIG_HIP(hipStreamSynchronize(s));
-  return !hflag;
-}
-}  // namespace eigmi
-
-namespace {
-
-// Z (b columns) = Vdst R with Vdst M-orthonormal (CholQR twice); R (b x b upper, row-major) on
-// the host.  Vdst may equal Z.  The b x b factorisations run on the device (k_chol_small: the host
-// chol_upper / tri_upper_inv arithmetic).  One host round trip in the middle reads R0 back to pick
-// the second pass (reuse M Z or recompute it, below), one at the end brings R and the breakdown
-// flag back.  The pick is a heuristic: the spread of R0's diagonal is only a lower bound on
-// cond(R0), so an ill-conditioned block with an even diagonal can still take the reuse path (its
-// second pass then restores M-orthonormality to ~eps cond(Z) instead of ~eps).
+// Z (b columns) = Vdst R with Vdst M-orthonormal (subspace.h CholQr2); R (b x b upper, row-major) on
+// the host.  Vdst may equal Z.
 void mcholqr2(eig_blanczos_s &w, double *Z, double *Vdst, std::vector<double> &Rtot)
 {
-  CholQr2 q;
-  q.M = w.M;
-  q.ctx = w.M->ctx;
-  q.b = w.b;
-  q.n = w.n;
-  q.ld = w.ld;
-  q.own = w.own;
-  q.MZ = dptr(w.MZ);
-  q.small = w.small->d();
-  q.chol = w.chol->d();
+  const CholQr2 q =
+      cholqr_args(w.M->ctx, w.M, w.b, w.n, w.ld, w.own, w.MZ->d(), w.small->d(), w.chol->d(), false);
   EIG_CHECK(mcholqr2_mv(q, Z, Vdst, Rtot, w.cholqr_recomputed), EIG_ERR_BREAKDOWN,
             "block Lanczos: M-Gram of the new block is not positive definite (Krylov space exhausted)");
 }
@@ -265,9 +80,6 @@ void check_pair(const eig_mat_s *K, const eig_mat_s *M)
   EIG_CHECK(K->nb_rows_global == K->nb_cols, EIG_ERR_SHAPE, "block Lanczos: square matrices required");
 }
 
-}  // namespace
-
-namespace {
 void blanczos_create(eig_mat_t K, eig_mat_t M, eig_mat_t Ks, double sigma, int block, int max_steps, int degree,
                      double lmin, double lmax, unsigned seed, eig_blanczos_t *out, eig_mg_t mg = nullptr,
                      int cycles = 0)
@@ -327,8 +139,7 @@ void blanczos_create(eig_mat_t K, eig_mat_t M, eig_mat_t Ks, double sigma, int b
               const double v = gen(urbg);
               if (i >= rb && i < rb + n) h[((size_t)c * w->ld + w->own + (i - rb)) * 8 + j] = v;
             }
-        EIG_HIP(hipMemcpyAsync(w->Xa->d(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        EIG_HIP(hipStreamSynchronize(s));
+        upload(h, w->Xa->d(), s);
       }
       std::vector<double> R;
       mcholqr2(*w, w->Xa->d(), w->V->d(), R);  // V_0 = M-orthonormal start block
@@ -388,21 +199,13 @@ extern "C" int eig_blanczos_step(eig_blanczos_t w, int steps, eig_blanczos_timin
     const int b = w->b;
     const i64 n = w->n, ld = w->ld, own = w->own;
     const size_t bs = (size_t)ld * b;  // doubles per basis block
-    std::vector<hipEvent_t> ev((size_t)5 * steps);
-    for (auto &e : ev) EIG_HIP(hipEventCreate(&e));
-    struct EvGuard {
-      std::vector<hipEvent_t> &v;
-      ~EvGuard()
-      {
-        for (auto &e : v) (void)hipEventDestroy(e);
-      }
-    } evg{ev};
+    TimingEvents ev((size_t)5 * steps);
     double *Ad = w->small->d();
     double *Cd = Ad + (size_t)b * b;
     for (int i = 0; i < steps; ++i)
     {
       const int j = w->k;
-      hipEvent_t *e = &ev[(size_t)5 * i];
+      hipEvent_t *e = ev.data() + (size_t)5 * i;
       double *Vj = w->V->d() + (size_t)j * bs;
       EIG_HIP(hipEventRecord(e[0], s));
       double *Z;
@@ -460,9 +263,7 @@ extern "C" int eig_blanczos_step(eig_blanczos_t w, int steps, eig_blanczos_timin
       std::vector<double> R;
       mcholqr2(*w, Z, w->V->d() + (size_t)(j + 1) * bs, R);  // syncs
       EIG_HIP(hipEventRecord(e[4], s));
-      for (int r = 0; r < b; ++r)
-        for (int c = r + 1; c < b; ++c)
-          Ah[(size_t)r * b + c] = Ah[(size_t)c * b + r] = 0.5 * (Ah[(size_t)r * b + c] + Ah[(size_t)c * b + r]);
+      symmetrise(b, Ah);
       w->A.insert(w->A.end(), Ah.begin(), Ah.end());
       w->B.insert(w->B.end(), R.begin(), R.end());
       w->k = j + 1;
@@ -473,7 +274,7 @@ extern "C" int eig_blanczos_step(eig_blanczos_t w, int steps, eig_blanczos_timin
       std::memset(timing, 0, sizeof(*timing));
       for (int i = 0; i < steps; ++i)
       {
-        hipEvent_t *e = &ev[(size_t)5 * i];
+        hipEvent_t *e = ev.data() + (size_t)5 * i;
         float t[4] = {0, 0, 0, 0};
         for (int q = 0; q < 4; ++q) EIG_HIP(hipEventElapsedTime(&t[q], e[q], e[q + 1]));
         timing->kspmm_ms += t[0];
@@ -494,29 +295,6 @@ extern "C" int eig_blanczos_step(eig_blanczos_t w, int steps, eig_blanczos_timin
   });
 }
 
-namespace {
-// The block tridiagonal T (k b x k b, row-major) of the k completed steps.
-std::vector<double> assemble_T(const eig_blanczos_s &w)
-{
-  const int b = w.b, k = w.k, N = k * b;
-  std::vector<double> T((size_t)N * N, 0.0);
-  for (int j = 0; j < k; ++j)
-  {
-    for (int r = 0; r < b; ++r)
-      for (int c = 0; c < b; ++c) T[(size_t)(j * b + r) * N + j * b + c] = w.A[((size_t)j * b + r) * b + c];
-    if (j + 1 < k)  // T_{j+1,j} = B_{j+1}, T_{j,j+1} = B_{j+1}^T
-      for (int r = 0; r < b; ++r)
-        for (int c = 0; c < b; ++c)
-        {
-          const double v = w.B[((size_t)j * b + r) * b + c];
-          T[(size_t)((j + 1) * b + r) * N + j * b + c] = v;
-          T[(size_t)(j * b + c) * N + (j + 1) * b + r] = v;
-        }
-  }
-  return T;
-}
-}  // namespace
-
 extern "C" int eig_blanczos_tmatrix(eig_blanczos_t w, int *dim, double *T_host)
 {
   return guard(w ? w->K->ctx : nullptr, [&] {
@@ -524,7 +302,7 @@ extern "C" int eig_blanczos_tmatrix(eig_blanczos_t w, int *dim, double *T_host)
     *dim = w->k * w->b;
     if (T_host)
     {
-      std::vector<double> T = assemble_T(*w);
+      std::vector<double> T = block_tridiag(w->b, w->k, w->A, w->B);
       std::memcpy(T_host, T.data(), T.size() * sizeof(double));
     }
   });
@@ -541,25 +319,13 @@ extern "C" int eig_blanczos_ritz(eig_blanczos_t w, int nev, int which, double *e
     eig_ctx_t ctx = w->K->ctx;
     EIG_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    std::vector<double> T = assemble_T(*w), th, S;
+    std::vector<double> T = block_tridiag(b, w->k, w->A, w->B), th, S;
     sym_eig(N, T, th, S);
     std::vector<int> pick(nev);
     if (!w->si)
       for (int i = 0; i < nev; ++i) pick[i] = (which == EIG_WHICH_LA) ? N - 1 - i : i;
     else
-    {
-      // the nev Ritz values of OP of largest |theta| (eigenvalues nearest sigma), ordered by
-      // lambda = sigma + 1 / theta: ascending (SA) or descending (LA)
-      std::vector<int> ord(N);
-      for (int i = 0; i < N; ++i) ord[i] = i;
-      std::stable_sort(ord.begin(), ord.end(), [&](int a, int c) { return std::fabs(th[a]) > std::fabs(th[c]); });
-      ord.resize(nev);
-      for (int i = 0; i < N; ++i) th[i] = th[i] != 0.0 ? w->sigma + 1.0 / th[i] : HUGE_VAL;
-      std::stable_sort(ord.begin(), ord.end(), [&](int a, int c) {
-        return which == EIG_WHICH_SA ? th[a] < th[c] : th[a] > th[c];
-      });
-      pick = ord;
-    }
+      si_ritz_order(th, w->sigma, nev, which, pick);  // th <- lambda = sigma + 1 / theta
     for (int i = 0; i < nev; ++i) eval_host[i] = th[pick[i]];
     if (!evec_host && !resid_host) return;
     const i64 n = w->n, ld = w->ld, own = w->own;
@@ -588,22 +354,18 @@ extern "C" int eig_blanczos_ritz(eig_blanczos_t w, int nev, int which, double *e
         EIG_HIP(hipMemcpyAsync(hk.data(), w->W->d(), hk.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         EIG_HIP(hipMemcpyAsync(hm.data(), w->MZ->d(), hm.size() * sizeof(double), hipMemcpyDeviceToHost, s));
       }
-      EIG_HIP(hipMemcpyAsync(hy.data(), Y, hy.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
+      download(hy, Y, s);  // (the sync covers hk and hm too)
       for (int c = 0; c < nc; ++c)
       {
         const int blk = c / 8, jj = c % 8;
         const double theta = th[pick[c0 + c]];
         double r2 = 0.0;
-        for (i64 r = 0; r < n; ++r)
+        if (evec_host) mv8_column(hy.data(), ld, own, n, c, 1.0, evec_host + (size_t)(c0 + c) * n);
+        for (i64 r = 0; resid_host && r < n; ++r)
         {
           const size_t at = ((size_t)blk * ld + own + r) * 8 + jj;
-          if (evec_host) evec_host[(size_t)(c0 + c) * n + r] = hy[at];
-          if (resid_host)
-          {
-            const double d = hk[at] - theta * hm[at];
-            r2 += d * d;
-          }
+          const double d = hk[at] - theta * hm[at];
+          r2 += d * d;
         }
         rs[c0 + c] = r2;
       }
@@ -622,56 +384,5 @@ extern "C" int eig_blanczos_ritz(eig_blanczos_t w, int nev, int which, double *e
 
 extern "C" int eig_blanczos_destroy(eig_blanczos_t w)
 {
-  if (!w) return EIG_OK;
-  (void)hipSetDevice(w->K->ctx->device);
-  (void)hipStreamSynchronize(w->K->ctx->stream);
-  delete w;
-  return EIG_OK;
-}
-
-// M^-1 B by the Chebyshev-Jacobi semi-iteration (the block Lanczos operator's inner solve).
-extern "C" int eig_mass_solve_mv8(eig_mat_t M, int64_t m, int degree, double lmin, double lmax, const double *B,
-                                  double *X)
-{
-  return guard(M ? M->ctx : nullptr, [&] {
-    EIG_CHECK(M && B && X && m > 0 && m % 8 == 0 && degree >= 1 && lmin > 0.0 && lmax > lmin, EIG_ERR_ARG,
-              "eig_mass_solve_mv8: bad argument");
-    EIG_CHECK(M->br == M->bc && M->br >= 1 && M->br <= 4 && M->nb_rows_global == M->nb_cols &&
-                  (M->br == 1 || !M->ctx->distributed()),
-              EIG_ERR_BLOCKSIZE,
-              "eig_mass_solve_mv8: square matrix of FieldMatrix<double,b,b>, b = 1..4 (b > 1: one rank)");
-    EIG_CHECK(X != B, EIG_ERR_ARG, "eig_mass_solve_mv8: X must not alias B (B is read by every step)");
-    eig_ctx_t ctx = M->ctx;
-    EIG_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const size_t bytes = (size_t)M->window * m * sizeof(double);
-    DevBuf dinv((size_t)std::max<i64>(M->nb_rows * M->br, 1) * sizeof(double)), Xb(bytes), Xc(bytes);
-    launch_diag_inv(*M, dinv.d(), s);
-    EIG_HIP(hipMemsetAsync(X, 0, bytes, s));
-    double *res = cheb_solve(*M, m, degree, lmin, lmax, B, dinv.d(), X, Xb.d(), Xc.d(), s);
-    if (res != X) EIG_HIP(hipMemcpyAsync(X, res, bytes, hipMemcpyDeviceToDevice, s));
-    EIG_HIP(hipStreamSynchronize(s));
-  });
-}
-
-extern "C" int eig_panel_update_mv8(eig_ctx_t ctx, int64_t n, int64_t m1, int64_t m2, const double *Q, const double *S,
-                                    double alpha, double beta, double *Y)
-{
-  return guard(ctx, [&] {
-    EIG_CHECK(ctx && Q && S && Y && n >= 0 && m1 >= 0 && m1 % 8 == 0 && m2 % 8 == 0 && m2 >= 8 && m2 <= 32,
-              EIG_ERR_ARG, "eig_panel_update_mv8: m1 % 8 == 0, m2 in {8,16,24,32}");
-    EIG_HIP(hipSetDevice(ctx->device));
-    launch_panel_update(n, n, n, m1, m2, Q, S, alpha, beta, Y, ctx->stream);
-  });
-}
-
-extern "C" int eig_panel_gram_mv8(eig_ctx_t ctx, int64_t n, int64_t m1, int64_t m2, const double *Q1, const double *Q2,
-                                  double *G)
-{
-  return guard(ctx, [&] {
-    EIG_CHECK(ctx && Q1 && Q2 && G && n >= 0 && m1 > 0 && m2 > 0 && m1 % 8 == 0 && m2 % 8 == 0, EIG_ERR_ARG,
-              "eig_panel_gram_mv8: bad argument");
-    EIG_HIP(hipSetDevice(ctx->device));
-    launch_panel_gram(ctx, n, n, m1, m2, Q1, Q2, G, ctx->stream);
-  });
+  return w ? destroy_workspace(w, w->K->ctx) : EIG_OK;
 }

@@ -330,7 +330,7 @@ void halo_staging_ensure(eig_ctx_t ctx, const std::vector<i64> &all, int bc)
   const int P = ctx->nranks;
   if (ctx->loop || P <= 1 || !ctx->mailbox_ready()) return;
   // the halo mailbox's slots hold the largest range of any rank's plan, 8 columns wide
-  // (blanczos.cpp exchanges blocks of 8); grown collectively when a matrix needs more
+  // (subspace.cpp halo_mv exchanges blocks of 8); grown collectively when a matrix needs more
   i64 most = 0;
   std::vector<int64_t> qr(3 * (size_t)P), qs(3 * (size_t)P);
   for (int q = 0; q < P; ++q)

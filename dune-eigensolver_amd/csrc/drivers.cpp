@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "inverse_common.h"
+#include "subspace.h"
 
 using namespace eigmi;
 
@@ -42,26 +43,6 @@ struct SyncEvent {
   SyncEvent(const SyncEvent &) = delete;
   SyncEvent &operator=(const SyncEvent &) = delete;
 };
-
-// evec[j][i] = Q(i, j): column j of the MultiVector<double,8> blocks sits at Q + (j/8)*8n + i*8 + j%8
-void copy_evecs(eig_ctx_t ctx, const double *Q, i64 n, int nev, double *evec_host)
-{
-  if (!evec_host) return;
-  const i64 m = (nev + 7) / 8 * 8;
-  std::vector<double> h((size_t)(n * m));
-  EIG_HIP(hipMemcpyAsync(h.data(), Q, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  EIG_HIP(hipStreamSynchronize(ctx->stream));
-  for (int j = 0; j < nev; ++j)
-    for (i64 i = 0; i < n; ++i) evec_host[(i64)j * n + i] = h[((j / 8) * n + i) * 8 + j % 8];
-}
-
-void random_block(eig_ctx_t ctx, i64 n, i64 m, unsigned seed, double *Q)
-{
-  std::vector<double> h((size_t)(n * m));
-  host_random_normal(n * m, seed, h.data());  // eigensolver.hh:50-55 / :137-142 / :222-227
-  EIG_HIP(hipMemcpyAsync(Q, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  EIG_HIP(hipStreamSynchronize(ctx->stream));
-}
 
 const char *const kFactorMismatch = "matmul_inverse_tallskinny_blocked: Factorization does not match size of Qout/Qin";
 
@@ -149,7 +130,7 @@ extern "C" int eig_standard_largest(eig_mat_t A, double shift, double tol, int m
       if (k > 1 && dist < tol) break;
     }
     for (int j = 0; j < nev; ++j) eval_host[j] = s2[j];
-    copy_evecs(ctx, B[basis], n, nev, evec_host);  // (the queued look-ahead iteration leaves this block alone)
+    copy_evecs(ctx, B[basis], n, 0, n, nev, nullptr, nullptr, evec_host);  // (the queued look-ahead iteration leaves this block alone)
     EIG_HIP(hipStreamSynchronize(s));  // the look-ahead iteration uses this call's buffers
     mgs_lookahead_check(ctx);          // a timed-out MGS barrier: EIG_ERR_HIP, never NaN with EIG_OK
     if (iters) *iters = kk;
@@ -217,7 +198,7 @@ extern "C" int eig_standard_inverse(eig_mat_t A, eig_lu_t lu, double shift, doub
       if (k > 1 && dist < tol) break;
     }
     for (int j = 0; j < nev; ++j) eval_host[j] = s2[j];
-    copy_evecs(ctx, Bk[basis], n, nev, evec_host);  // (stream order: after any queued iteration)
+    copy_evecs(ctx, Bk[basis], n, 0, n, nev, nullptr, nullptr, evec_host);  // (stream order: after any queued iteration)
     EIG_HIP(hipStreamSynchronize(s));
     mgs_lookahead_check(ctx);
     if (iters) *iters = kk;
@@ -299,7 +280,7 @@ extern "C" int eig_generalized_inverse(eig_mat_t A, eig_mat_t B, eig_lu_t lu, do
       if ((iter > 10) & (relerror < tol)) break;  // :325
     }
     for (int j = 0; j < nev; ++j) eval_host[j] = ra2[j];
-    copy_evecs(ctx, Bk[basis], n, nev, evec_host);  // (stream order: after any queued iteration)
+    copy_evecs(ctx, Bk[basis], n, 0, n, nev, nullptr, nullptr, evec_host);  // (stream order: after any queued iteration)
     EIG_HIP(hipStreamSynchronize(s));
     if (iters) *iters = iter;
     if (verbose > 0) fprintf(stdout, "GeneralizedInverse: iterations=%d relerror=%.17g\n", iter, relerror);
@@ -491,15 +472,14 @@ struct eig_lanczos_s {
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   int g_steps = 0, g_flags = 0;
-  std::vector<hipEvent_t> g_ev;  // [beg, end, events_per_step(g_flags) per step]
+  std::unique_ptr<TimingEvents> g_ev;  // [beg, end, events_per_step(g_flags) per step]
   void drop_graph()
   {
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
-    for (auto &e : g_ev) (void)hipEventDestroy(e);
     gexec = nullptr;
     graph = nullptr;
-    g_ev.clear();
+    g_ev.reset();
     g_steps = 0;
   }
   ~eig_lanczos_s()
@@ -634,7 +614,8 @@ void fused_state(eig_lanczos_s &ws, int &j, int &mode)
 }
 
 void read_timing(const std::vector<hipEvent_t> &ev, int steps, int nps, eig_timing *timing, bool accumulate = false);
-std::vector<hipEvent_t> make_events(int steps, int nps);
+// events of a batch of steps: [beg, end, nps per step]
+size_t batch_events(int steps, int nps) { return 2 + (size_t)nps * steps; }
 
 // After `launched` fused launches were enqueued for logical steps up to `target`: synchronise, then
 // top up with eager launches until the target step is reached (launches that repaired took no
@@ -653,28 +634,12 @@ void fused_settle(eig_lanczos_s &ws, int target, int nps, eig_timing *timing)
     if (j >= target) return;
     const int more = target - j;
     EIG_CHECK(ws.L + more <= ws.max_launches, EIG_ERR_ARG, "fused Lanczos: launch capacity exhausted");
-    std::vector<hipEvent_t> ev = make_events(more, nps);
-    try
-    {
-      enqueue_steps(ws, more, nps, ev.data(), false);
-      EIG_HIP(hipStreamSynchronize(ctx->stream));
-      ws.L += more;
-      read_timing(ev, more, nps, timing, true);
-    }
-    catch (...)
-    {
-      for (auto &e : ev) (void)hipEventDestroy(e);
-      throw;
-    }
-    for (auto &e : ev) (void)hipEventDestroy(e);
+    TimingEvents ev(batch_events(more, nps));
+    enqueue_steps(ws, more, nps, ev.data(), false);
+    EIG_HIP(hipStreamSynchronize(ctx->stream));
+    ws.L += more;
+    read_timing(ev.ev, more, nps, timing, true);
   }
-}
-
-std::vector<hipEvent_t> make_events(int steps, int nps)
-{
-  std::vector<hipEvent_t> ev(2 + (size_t)nps * steps);
-  for (auto &e : ev) EIG_HIP(hipEventCreate(&e));
-  return ev;
 }
 
 void read_timing(const std::vector<hipEvent_t> &ev, int steps, int nps, eig_timing *timing, bool accumulate)
@@ -789,21 +754,14 @@ extern "C" int eig_lanczos_step(eig_lanczos_t ws, int steps, int flags, eig_timi
     EIG_HIP(hipSetDevice(ctx->device));
     const int nps = events_per_step(flags);
     const int target = ws->k + steps;
-    std::vector<hipEvent_t> ev = make_events(steps, nps);
-    try
     {
+      TimingEvents ev(batch_events(steps, nps));
       enqueue_steps(*ws, steps, nps, ev.data(), false);
       EIG_HIP(hipStreamSynchronize(ctx->stream));
       if (ws->fused) ws->L += steps;
       else ws->k += steps;
-      read_timing(ev, steps, nps, timing);
+      read_timing(ev.ev, steps, nps, timing);
     }
-    catch (...)
-    {
-      for (auto &e : ev) (void)hipEventDestroy(e);
-      throw;
-    }
-    for (auto &e : ev) (void)hipEventDestroy(e);
     if (ws->fused) fused_settle(*ws, target, nps, timing);
   });
 }
@@ -843,7 +801,7 @@ extern "C" int eig_lanczos_capture(eig_lanczos_t ws, int steps, int flags, int *
     EIG_HIP(hipSetDevice(ctx->device));
     ws->g_steps = steps;
     ws->g_flags = flags;
-    ws->g_ev = make_events(steps, events_per_step(flags));
+    ws->g_ev.reset(new TimingEvents(batch_events(steps, events_per_step(flags))));
     if (captured) *captured = 0;
     // the loopback transport synchronises with the host inside the step: eager replay only
     if (ctx->loopback()) return;
@@ -855,7 +813,7 @@ extern "C" int eig_lanczos_capture(eig_lanczos_t ws, int steps, int flags, int *
     bool ok = true;
     try
     {
-      enqueue_steps(*ws, steps, events_per_step(flags), ws->g_ev.data(), true);
+      enqueue_steps(*ws, steps, events_per_step(flags), ws->g_ev->data(), true);
     }
     catch (...)
     {
@@ -894,11 +852,11 @@ extern "C" int eig_lanczos_replay(eig_lanczos_t ws, eig_timing *timing)
     if (ws->gexec)
       EIG_HIP(hipGraphLaunch(ws->gexec, s));
     else
-      enqueue_steps(*ws, steps, nps, ws->g_ev.data(), false);
+      enqueue_steps(*ws, steps, nps, ws->g_ev->data(), false);
     EIG_HIP(hipStreamSynchronize(s));
     if (ws->fused) ws->L += steps;
     else ws->k += steps;
-    read_timing(ws->g_ev, steps, nps, timing);
+    read_timing(ws->g_ev->ev, steps, nps, timing);
     ws->drop_graph();
     if (ws->fused) fused_settle(*ws, target, nps, timing);
   });

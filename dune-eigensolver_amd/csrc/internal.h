@@ -475,26 +475,7 @@ void launch_panel_gram(eig_ctx_t ctx, i64 n, i64 ld, i64 m1, i64 m2, const doubl
                        hipStream_t s);
 void launch_panel_gram_2stage(eig_ctx_t ctx, i64 n, i64 ld, i64 m1, i64 m2, const double *Q1, const double *Q2,
                               double *G, hipStream_t s);
-// Chebyshev-Jacobi semi-iteration for M X = Bv (degree steps on the spectrum bounds [lmin, lmax]
-// of diag(M)^-1 M, from X = 0; blanczos.cpp): returns the buffer (Xa, Xb or Xc) holding x_degree.
-double *cheb_solve(eig_mat_s &M, i64 m, int degree, double lmin, double lmax, const double *Bv, const double *dinv,
-                   double *Xa, double *Xb, double *Xc, hipStream_t s);
-// CholQR2 in the M-inner product (blanczos.cpp; block Lanczos and LOBPCG): Z (b columns) = Vdst R with
-// Vdst M-orthonormal, R (b x b upper, row-major) to the host in Rtot.  Vdst may equal Z.  M == nullptr is
-// M = I (MZ unused).  finish_mz: MZ = M Vdst on return (the factors applied to M Z as to Z; the fused
-// b = 32 middle step, which never stores M Z R0^-1, is then not taken).  `recomputed` counts second
-// passes that recomputed M Z.  False on a non-positive pivot (Vdst is then not usable).
-struct CholQr2 {
-  eig_mat_s *M = nullptr;
-  eig_ctx_t ctx = nullptr;
-  int b = 0;
-  i64 n = 0, ld = 0, own = 0;
-  double *MZ = nullptr;     // b columns, window layout
-  double *small = nullptr;  // 2 b b doubles: Gram, inverse factor
-  double *chol = nullptr;   // 2 b b doubles + 64 bytes: R, Rtot and the flag
-  bool finish_mz = false;
-};
-bool mcholqr2_mv(const CholQr2 &q, double *Z, double *Vdst, std::vector<double> &Rtot, long long &recomputed);
+// (the Chebyshev-Jacobi solve cheb_solve and CholQR2 in the M-inner product, mcholqr2_mv: subspace.h)
 // LOBPCG's streaming kernels (k_lobpcg.hip).  R = KX - MX diag(theta) (m columns, leading dimension
 // ld, pointers at owned row 0) and sums[j] = ||r_j||^2, sums[m + j] = ||(MX)_j||^2 (device; tickets
 // 0 .. m / 8 - 1 and the partials of ctx->red).

@@ -818,7 +818,7 @@ __global__ __launch_bounds__(256) void k_panel_update(i64 n, i64 ldq, i64 ldy, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// CholQR's small factorisation on the device (block Lanczos, blanczos.cpp mcholqr2): one workgroup
+// CholQR's small factorisation on the device (subspace.cpp mcholqr2_mv): one workgroup
 // takes the b x b M-Gram G (b <= 32), symmetrises it, factors G = R^T R (upper R), inverts R and
 // folds R into the running product Rtot <- R Rtot (pass 0: Rtot = I).  The same operations in the
 // same order as the host chol_upper / tri_upper_inv (dense.cpp) and mcholqr2's product -- each
@@ -901,7 +901,7 @@ void launch_chol_small(int b, int pass, const double *G, double *R, double *Ri, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// CholQR2's middle step fused (blanczos.cpp mcholqr2, b = 32 columns = 4 blocks): with S = R^-1 of
+// CholQR2's middle step fused (subspace.cpp mcholqr2_mv, b = 32 columns = 4 blocks): with S = R^-1 of
 // the first pass (upper triangular, row-major 32 x 32), Z <- Z' = Z S and G = Z'^T (MZ S) in ONE
 // pass over Z and MZ -- MZ S (the first pass's update of M Z) is never stored, and Z' is not read
 // back for the second Gram.  Both products on v_mfma_f64_16x16x4f64, 16 rows per wave iteration:

@@ -231,7 +231,7 @@ void launch_gram_mv8(i64 n, i64 m1, i64 m2, const double *Q1, const double *Q2, 
   gram_dispatch(n, n, n, m1, m2, Q1, Q2, G, red.ticket(ticket), red.partials, (i64)kMaxRedBlocks * kMaxRedVals, s);
 }
 
-// Window-layout panels (block Lanczos, blanczos.cpp): column blocks ld rows apart; partials in a
+// Window-layout panels (block Lanczos, blanczos.cpp; CholQR2, subspace.cpp): column blocks ld rows apart; partials in a
 // context buffer sized for the launch, tickets from the context pool (the panel products run alone
 // on the stream, like every other reduction)
 void launch_gram_panel(eig_ctx_t ctx, i64 n, i64 ld, i64 m1, i64 m2, const double *Q1, const double *Q2, double *G,

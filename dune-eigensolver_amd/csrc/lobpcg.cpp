@@ -12,18 +12,21 @@
 //      iterations (mg_apply) -- a search direction only, so its accuracy does not enter the answer
 //   3. two classical Gram-Schmidt passes of W against [X P] in the M-inner product with the carried
 //      MX, MP (panel Gram + panel update; no M SpMM)
-//   4. M-CholQR2 of W (mcholqr2_mv, shared with blanczos.cpp; M W carried out of it), K W
-//   5. H = S^T K S (panel Gram), symmetrised, sym_eig on the host: C_x = the m wanted eigenvectors
+//   4. M-CholQR2 of W (subspace.h mcholqr2_mv; M W carried out of it), K W
+//   5. H = S^T K S (panel Gram), symmetrised, sym_eig on the host: C_x = the m wanted eigenvectors (small_ritz)
 //   6. C_p = C_x with its X rows zeroed, orthogonalised twice against C_x, Householder QR
+//      (subspace_host.h search_coefficients)
 //   7. [X' P'] = S [C_x C_p] on S, KS and MS (k_lobpcg_update)
 // A non-positive pivot in 4., or an S that is not M-orthonormal to kOrthTol after 4. (checked by one panel
 // Gram S^T M S), redoes the iteration without P; without P it is EIG_ERR_BREAKDOWN.
+// The transfers, read-backs and checks shared with block Lanczos and slicing are subspace.h's, the host
+// arithmetic of 1., 5., 6. and the orthonormality test subspace_host.h's.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "internal.h"
+#include "subspace.h"
 
 using namespace eigmi;
 
@@ -71,131 +74,16 @@ namespace {
 
 bool cholqr(eig_lobpcg_s &w, double *Z, double *MZ)
 {
-  CholQr2 q;
-  q.M = w.M;
-  q.ctx = w.K->ctx;
-  q.b = w.m;
-  q.n = q.ld = w.n;
-  q.own = 0;
-  q.MZ = MZ;
-  q.small = w.Qd();
-  q.chol = w.chol->d();
-  q.finish_mz = true;
+  const CholQr2 q = cholqr_args(w.K->ctx, w.M, w.m, w.n, w.n, 0, MZ, w.Qd(), w.chol->d(), true);
   std::vector<double> R;
   return mcholqr2_mv(q, Z, Z, R, w.cholqr_recomputed);
 }
 
-void upload(const std::vector<double> &h, double *d, hipStream_t s)
-{
-  EIG_HIP(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  EIG_HIP(hipStreamSynchronize(s));  // h is pageable and may go out of scope
-}
-
-// H (N x N, row-major, device) symmetrised and diagonalised: the m wanted eigenpairs, theta in the
-// order of `which` (SA ascending, LA descending), Cx (N x m, row-major) their eigenvectors
-void ritz_small(const eig_lobpcg_s &w, int N, const double *Hdev, std::vector<double> &theta, std::vector<double> &Cx,
-                hipStream_t s)
-{
-  const int m = w.m;
-  std::vector<double> H((size_t)N * N), ev, Z;
-  EIG_HIP(hipMemcpyAsync(H.data(), Hdev, H.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  EIG_HIP(hipStreamSynchronize(s));
-  for (int r = 0; r < N; ++r)
-    for (int c = r + 1; c < N; ++c)
-      H[(size_t)r * N + c] = H[(size_t)c * N + r] = 0.5 * (H[(size_t)r * N + c] + H[(size_t)c * N + r]);
-  sym_eig(N, H, ev, Z);
-  theta.resize(m);
-  Cx.assign((size_t)N * m, 0.0);
-  for (int j = 0; j < m; ++j)
-  {
-    const int pick = w.which == EIG_WHICH_LA ? N - 1 - j : j;
-    theta[j] = ev[pick];
-    for (int r = 0; r < N; ++r) Cx[(size_t)r * m + j] = Z[(size_t)r * N + pick];
-  }
-}
-
-// Q (N x m, row-major) = the orthonormal factor of A's Householder QR (A: N x m, N >= m, overwritten)
-void householder_q(int N, int m, std::vector<double> &A, std::vector<double> &Q)
-{
-  std::vector<double> V((size_t)N * m, 0.0), beta(m, 0.0);  // reflector j: I - beta_j v_j v_j^T, v_j in column j
-  for (int j = 0; j < m; ++j)
-  {
-    double nrm = 0.0;
-    for (int r = j; r < N; ++r) nrm += A[(size_t)r * m + j] * A[(size_t)r * m + j];
-    nrm = std::sqrt(nrm);
-    if (nrm == 0.0) continue;  // a zero column: no reflector (Q keeps the unit vector e_j)
-    const double a = A[(size_t)j * m + j];
-    const double alpha = a >= 0.0 ? -nrm : nrm;
-    for (int r = j; r < N; ++r) V[(size_t)r * m + j] = A[(size_t)r * m + j];
-    V[(size_t)j * m + j] = a - alpha;
-    double vv = 0.0;
-    for (int r = j; r < N; ++r) vv += V[(size_t)r * m + j] * V[(size_t)r * m + j];
-    if (vv == 0.0) continue;
-    beta[j] = 2.0 / vv;
-    for (int c = j; c < m; ++c)
-    {
-      double d = 0.0;
-      for (int r = j; r < N; ++r) d += V[(size_t)r * m + j] * A[(size_t)r * m + c];
-      d *= beta[j];
-      for (int r = j; r < N; ++r) A[(size_t)r * m + c] -= d * V[(size_t)r * m + j];
-    }
-  }
-  Q.assign((size_t)N * m, 0.0);
-  for (int j = 0; j < m; ++j) Q[(size_t)j * m + j] = 1.0;
-  for (int j = m - 1; j >= 0; --j)
-  {
-    if (beta[j] == 0.0) continue;
-    for (int c = 0; c < m; ++c)
-    {
-      double d = 0.0;
-      for (int r = j; r < N; ++r) d += V[(size_t)r * m + j] * Q[(size_t)r * m + c];
-      d *= beta[j];
-      for (int r = j; r < N; ++r) Q[(size_t)r * m + c] -= d * V[(size_t)r * m + j];
-    }
-  }
-}
-
-// C = [C_x C_p] (N x 2 m, row-major): C_p = C_x with its X rows (the first m) zeroed, orthogonalised
-// twice against C_x, then orthonormalised
-void search_coefficients(int N, int m, const std::vector<double> &Cx, std::vector<double> &C)
-{
-  std::vector<double> Cp = Cx, G((size_t)m * m), Q;
-  std::fill(Cp.begin(), Cp.begin() + (size_t)m * m, 0.0);
-  for (int pass = 0; pass < 2; ++pass)
-  {
-    for (int a = 0; a < m; ++a)
-      for (int b = 0; b < m; ++b)
-      {
-        double d = 0.0;
-        for (int r = 0; r < N; ++r) d += Cx[(size_t)r * m + a] * Cp[(size_t)r * m + b];
-        G[(size_t)a * m + b] = d;
-      }
-    for (int r = 0; r < N; ++r)
-      for (int b = 0; b < m; ++b)
-      {
-        double d = 0.0;
-        for (int a = 0; a < m; ++a) d += Cx[(size_t)r * m + a] * G[(size_t)a * m + b];
-        Cp[(size_t)r * m + b] -= d;
-      }
-  }
-  householder_q(N, m, Cp, Q);
-  C.assign((size_t)N * 2 * m, 0.0);
-  for (int r = 0; r < N; ++r)
-    for (int j = 0; j < m; ++j)
-    {
-      C[(size_t)r * 2 * m + j] = Cx[(size_t)r * m + j];
-      C[(size_t)r * 2 * m + m + j] = Q[(size_t)r * m + j];
-    }
-}
-
-// R = KX - MX diag(theta) into `dst`; rr[j] = ||r_j||^2, mm[j] = ||(MX)_j||^2 on the host
+// R = KX - MX diag(theta) into `dst`; sums[j] = ||r_j||^2, sums[m + j] = ||(MX)_j||^2 on the host
 void residual(eig_lobpcg_s &w, const double *KX, const double *MX, double *dst, std::vector<double> &sums,
               hipStream_t s)
 {
-  launch_lobpcg_resid(w.K->ctx, w.n, w.n, w.m, KX, MX, w.theta_d(), dst, w.sums_d(), s);
-  sums.resize((size_t)2 * w.m);
-  EIG_HIP(hipMemcpyAsync(sums.data(), w.sums_d(), sums.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  EIG_HIP(hipStreamSynchronize(s));
+  residual_sums(w.K->ctx, w.n, w.n, w.m, KX, MX, w.theta_d(), dst, w.sums_d(), sums, s);
 }
 
 // where the residual goes: straight into W without a preconditioner, else the preconditioner's input
@@ -237,15 +125,8 @@ bool iterate(eig_lobpcg_s &w, bool use_p, hipEvent_t *e)
     // failed orthonormalisation.
     launch_panel_gram(ctx, n, n, N, N, w.S->d(), MSf->d(), w.Hd(), s);
     std::vector<double> G((size_t)N * N);
-    EIG_HIP(hipMemcpyAsync(G.data(), w.Hd(), G.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    EIG_HIP(hipStreamSynchronize(s));
-    double dev = 0.0;
-    for (int r = 0; r < N; ++r)
-      for (int c = 0; c < N; ++c)
-      {
-        const double d = std::fabs(G[(size_t)r * N + c] - (r == c ? 1.0 : 0.0));
-        if (!(d <= dev)) dev = d == d ? d : HUGE_VAL;  // (a NaN counts as a miss)
-      }
+    download(G, w.Hd(), s);
+    const double dev = orth_deviation(N, G);
     if (!(dev <= kOrthTol))
     {
       ++w.orth_rejected;
@@ -258,7 +139,7 @@ bool iterate(eig_lobpcg_s &w, bool use_p, hipEvent_t *e)
   EIG_HIP(hipEventRecord(e[4], s));
   launch_panel_gram(ctx, n, n, N, N, w.S->d(), w.KS->d(), w.Hd(), s);
   std::vector<double> Cx, C;
-  ritz_small(w, N, w.Hd(), w.theta, Cx, s);
+  small_ritz(N, w.Hd(), m, w.which, w.theta, Cx, s);
   search_coefficients(N, m, Cx, C);
   upload(C, w.Cd(), s);
   launch_lobpcg_update(ctx, n, n, m, kb, w.S->d(), w.KS->d(), w.M ? w.MS->d() : nullptr, w.Cd(), s);
@@ -285,14 +166,9 @@ extern "C" int eig_lobpcg_create(eig_mat_t K, eig_mat_t M, int block, int which,
     EIG_CHECK(K && out && block >= 8 && block <= 32 && block % 8 == 0, EIG_ERR_ARG,
               "eig_lobpcg_create: K, ws and block in {8, 16, 24, 32} required");
     EIG_CHECK(which == EIG_WHICH_SA || which == EIG_WHICH_LA, EIG_ERR_ARG, "eig_lobpcg_create: bad `which`");
-    EIG_CHECK(!K->ctx->distributed(), EIG_ERR_ARG, "eig_lobpcg_create: one rank only");
-    EIG_CHECK(K->br == K->bc && K->br >= 1 && K->br <= 4, EIG_ERR_BLOCKSIZE,
-              "eig_lobpcg_create: square blocks FieldMatrix<double,b,b> with b = 1..4");
+    check_square_single_rank(K, "eig_lobpcg_create", ": square blocks FieldMatrix<double,b,b> with b = 1..4", false);
     if (M) check_matrix(M, K, "eig_lobpcg_create: M");
     const i64 n = K->nb_rows * K->br;
-    EIG_CHECK(K->nb_rows_global == K->nb_cols && K->nb_rows == K->nb_rows_global && K->window == n &&
-                  K->own_offset == 0,
-              EIG_ERR_SHAPE, "eig_lobpcg_create: square single-rank matrix required");
     EIG_CHECK((i64)4 * block <= n, EIG_ERR_SHAPE, "eig_lobpcg_create: 4 * block exceeds the matrix size");
     eig_ctx_t ctx = K->ctx;
     EIG_HIP(hipSetDevice(ctx->device));
@@ -317,18 +193,13 @@ extern "C" int eig_lobpcg_create(eig_mat_t K, eig_mat_t M, int block, int which,
       if (X0)
         EIG_HIP(hipMemcpyAsync(w->S->d(), X0, w->slice() * sizeof(double), hipMemcpyDeviceToDevice, s));
       else
-      {
-        // mt19937(seed) normals in MultiVector fill order (block, row, col) = the flat order (eig_random_mv8)
-        std::vector<double> h(w->slice());
-        host_random_normal((i64)h.size(), seed, h.data());
-        upload(h, w->S->d(), s);
-      }
+        random_block(ctx, n, m, seed, w->S->d());
       EIG_CHECK(cholqr(*w, w->X(w->S), w->X(w->MSf())), EIG_ERR_BREAKDOWN,
                 "eig_lobpcg_create: the start block is not of full rank in the M-inner product");
       launch_spmm_mv8(*K, m, w->X(w->S), w->X(w->KS), s);
       launch_panel_gram(ctx, n, n, m, m, w->X(w->S), w->X(w->KS), w->Hd(), s);
       std::vector<double> Cx;
-      ritz_small(*w, m, w->Hd(), w->theta, Cx, s);
+      small_ritz(m, w->Hd(), m, which, w->theta, Cx, s);
       upload(Cx, w->Cd(), s);
       for (DevBuf *d : {w->S, w->KS, w->MS})
         if (d) launch_panel_update(n, n, n, m, m, d->d(), w->Cd(), 1.0, 0.0, d->d(), s);
@@ -395,20 +266,7 @@ extern "C" int eig_lobpcg_step(eig_lobpcg_t w, int max_iters, int nev, double to
     eig_ctx_t ctx = w->K->ctx;
     EIG_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    hipEvent_t ev[6];
-    std::vector<hipEvent_t> made;
-    struct EvGuard {
-      std::vector<hipEvent_t> &v;
-      ~EvGuard()
-      {
-        for (auto &e : v) (void)hipEventDestroy(e);
-      }
-    } evg{made};
-    for (auto &e : ev)
-    {
-      EIG_HIP(hipEventCreate(&e));
-      made.push_back(e);
-    }
+    TimingEvents ev(6);
     if (iters_done) *iters_done = 0;
     if (converged) *converged = 0;
     if (timing) std::memset(timing, 0, sizeof(*timing));
@@ -423,12 +281,10 @@ extern "C" int eig_lobpcg_step(eig_lobpcg_t w, int max_iters, int nev, double to
       EIG_HIP(hipEventRecord(ev[1], s));
       if (tol > 0.0)
       {
-        conv = true;
-        for (int j = 0; j < nev; ++j)
-          conv = conv && std::sqrt(sums[j]) <= tol * std::fabs(w->theta[j]) * std::sqrt(sums[w->m + j]);
+        conv = lobpcg_converged(sums, w->theta, w->m, nev, tol);
         if (conv || it == max_iters) break;
       }
-      if (!iterate(*w, w->has_p, ev))
+      if (!iterate(*w, w->has_p, ev.data()))
       {
         EIG_CHECK(w->has_p, EIG_ERR_BREAKDOWN,
                   "LOBPCG: W has no positive-definite M-Gram, or [X W] is not M-orthonormal after CholQR2");
@@ -438,7 +294,7 @@ extern "C" int eig_lobpcg_step(eig_lobpcg_t w, int max_iters, int nev, double to
         EIG_HIP(hipEventRecord(ev[0], s));
         residual(*w, w->X(w->KS), w->X(w->MSf()), res_buf(*w), sums, s);
         EIG_HIP(hipEventRecord(ev[1], s));
-        EIG_CHECK(iterate(*w, false, ev), EIG_ERR_BREAKDOWN,
+        EIG_CHECK(iterate(*w, false, ev.data()), EIG_ERR_BREAKDOWN,
                   "LOBPCG: W has no positive-definite M-Gram, or [X W] is not M-orthonormal after CholQR2 (without P too)");
       }
       w->has_p = true;
@@ -490,25 +346,13 @@ extern "C" int eig_lobpcg_ritz(eig_lobpcg_t w, int nev, double *eval_host, doubl
       residual(*w, w->W(w->KS), w->M ? w->W(w->MS) : w->X(w->S), res_buf(*w), sums, s);
       for (int j = 0; j < nev; ++j) resid_host[j] = std::sqrt(sums[j]);
     }
-    if (evec_host)
-    {
-      const int nblk = (nev + 7) / 8;
-      std::vector<double> h((size_t)nblk * n * 8);
-      EIG_HIP(hipMemcpyAsync(h.data(), w->S->d(), h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
-      for (int j = 0; j < nev; ++j)
-        for (i64 r = 0; r < n; ++r) evec_host[(size_t)j * n + r] = h[((size_t)(j / 8) * n + r) * 8 + j % 8];
-    }
+    copy_evecs(ctx, w->S->d(), n, 0, n, nev, nullptr, nullptr, evec_host);
   });
 }
 
 extern "C" int eig_lobpcg_destroy(eig_lobpcg_t w)
 {
-  if (!w) return EIG_OK;
-  (void)hipSetDevice(w->K->ctx->device);
-  (void)hipStreamSynchronize(w->K->ctx->stream);
-  delete w;
-  return EIG_OK;
+  return w ? destroy_workspace(w, w->K->ctx) : EIG_OK;
 }
 
 extern "C" int eig_lobpcg_resid_mv8(eig_ctx_t ctx, int64_t n, int64_t m, const double *KX, const double *MX,

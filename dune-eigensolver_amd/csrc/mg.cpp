@@ -38,8 +38,8 @@
 #include <vector>
 
 #include "amg_setup.h"
-#include "internal.h"
 #include "mg_setup.h"
+#include "subspace.h"
 
 using namespace eigmi;
 
@@ -118,20 +118,20 @@ struct eig_mg_s {
 
 namespace {
 
-// Chebyshev semi-iteration with block Jacobi on square blocks 2..4: cheb_solve's recurrence (blanczos.cpp) with
+// Chebyshev semi-iteration with block Jacobi on square blocks 2..4: cheb_solve's recurrence (subspace.cpp) with
 // z = D_I^-1 (b - M x_k) per node; the in-place two-buffer form.  Returns the buffer holding x_degree.
 double *cheb_solve_bjac(eig_mat_s &M, i64 m, int degree, double lmin, double lmax, const double *Bv, const double *binv,
                         double *Xa, double *Xb, hipStream_t s)
 {
-  const double gamma = 2.0 / (lmin + lmax), mu = (lmax - lmin) / (lmax + lmin);
-  double omega = 1.0 / (1.0 - 0.5 * mu * mu);  // omega_1
-  launch_cheb_init_bjac(M, m, Bv, binv, gamma, Xa, s);
+  const ChebJacobi cj(lmin, lmax);
+  double omega = cj.omega1();
+  launch_cheb_init_bjac(M, m, Bv, binv, cj.gamma, Xa, s);
   if (degree <= 1) return Xa;
   EIG_HIP(hipMemsetAsync(Xb, 0, (size_t)M.window * m * sizeof(double), s));  // x_0 = 0
   for (int k = 1; k < degree; ++k)
   {
-    if (k > 1) omega = 1.0 / (1.0 - 0.25 * mu * mu * omega);
-    launch_cheb_step_bjac(M, m, Xa, Xb, Bv, binv, omega, gamma, s);
+    if (k > 1) omega = cj.next(omega);
+    launch_cheb_step_bjac(M, m, Xa, Xb, Bv, binv, omega, cj.gamma, s);
     std::swap(Xa, Xb);
   }
   return Xa;
@@ -185,8 +185,8 @@ double *vcycle(eig_mg_s &mg, size_t l, i64 m, const double *b)
   launch_resid_mv8(*L.A, m, x, b, T, s);  // T = b - A x
   // x += post-smoothing correction: a degree-2 smoother on the row-class image adds its x_2 in
   // place (cheb_solve's first step, its gamma and omega_1); 1x1 blocks only
-  const double gamma = 2.0 / (lo + hi), mu = (hi - lo) / (hi + lo);
-  if (L.b == 1 && mg.nu == 2 && launch_box_cheb_first_add(*L.A, m, T, 1.0 / (1.0 - 0.5 * mu * mu), gamma, x, s)) return x;
+  const ChebJacobi cj(lo, hi);
+  if (L.b == 1 && mg.nu == 2 && launch_box_cheb_first_add(*L.A, m, T, cj.omega1(), cj.gamma, x, s)) return x;
   double *q[3];
   for (int i = 0, j = 0; i < 4; ++i)
     if (C[i] != x) q[j++] = C[i];
@@ -500,8 +500,7 @@ extern "C" int eig_mg_solve(eig_mg_t mg, int64_t m, const double *B, double *X, 
       launch_dot_diag_mv8(L.n, m, T, T, dp, 0, s, ctx->red);
       launch_dot_diag_mv8(L.n, m, B, B, dp + m, 0, s, ctx->red);
       std::vector<double> h((size_t)2 * m);
-      EIG_HIP(hipMemcpyAsync(h.data(), dp, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
+      download(h, dp, s);
       double r = 0.0;
       for (i64 j = 0; j < m; ++j) r = std::max(r, h[j] > 0.0 ? std::sqrt(h[j] / std::max(h[m + j], 1e-300)) : 0.0);
       *resid_host = r;

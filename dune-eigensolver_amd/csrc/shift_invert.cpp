@@ -2,6 +2,7 @@
 // Lanczos, one-vector and block (eig_shift_invert_solve[_ex] / _adaptive), and Arnoldi with Krylov-Schur restarts
 // (eig_arnoldi_shift_invert).  The one-vector paths share KrylovWs; their host arithmetic is krylov_host.cpp.
 #include "inverse_common.h"
+#include "subspace_host.h"
 
 using namespace eigmi;
 
@@ -503,8 +504,7 @@ void shift_invert_block_core(eig_mat_t A, eig_mat_t B, const LuRef &F, double si
     for (int q = 0; q < nev; ++q)
     {
       EIG_CHECK(xb[q] > 0.0, EIG_ERR_BREAKDOWN, "shift-invert: purified Ritz vector has no B-norm");
-      const double sc = 1.0 / std::sqrt(xb[q]);
-      for (i64 i = 0; i < n; ++i) evec_host[(i64)q * n + i] = sc * h[((i64)(q / 8) * n + i) * 8 + q % 8];
+      mv8_column(h.data(), n, 0, n, q, 1.0 / std::sqrt(xb[q]), evec_host + (i64)q * n);
     }
   }
   if (restarts) *restarts = nrestart;

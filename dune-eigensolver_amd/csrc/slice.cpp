@@ -12,14 +12,14 @@
 //   4. X = Y S, AX = W S (panel updates)
 //   5. Y = AX - X diag(theta) with the column sums ||r_j||^2, ||x_j||^2 (k_lobpcg_resid, MX = X)
 // The pairs with theta in [a, b] are accepted; the step stops when there is at least one and every one has
-// ||r_j|| <= tol max(|theta_j|, |a|, |b|) ||x_j||.
-#include <algorithm>
+// ||r_j|| <= tol max(|theta_j|, |a|, |b|) ||x_j|| (subspace_host.h window_converged).  CholQR2, the small
+// Rayleigh-Ritz read-back, the residual sums and the eigenvector copy-out are subspace.h's.
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "filter_host.h"
-#include "internal.h"
+#include "subspace.h"
 
 using namespace eigmi;
 
@@ -51,13 +51,7 @@ namespace {
 
 void check_filter_matrix(const eig_mat_s *A, const char *who)
 {
-  EIG_CHECK(!A->ctx->distributed(), EIG_ERR_ARG, std::string(who) + ": one rank only");
-  EIG_CHECK((A->br == 1 && A->bc == 1) || (A->br == A->bc && A->br >= 2 && A->br <= 4), EIG_ERR_BLOCKSIZE,
-            std::string(who) + ": 1x1 blocks or square blocks FieldMatrix<double,b,b> with b = 2..4");
-  const i64 n = A->nb_rows * A->br;
-  EIG_CHECK(A->nb_rows_global == A->nb_cols && A->nb_rows == A->nb_rows_global && A->window == n &&
-                A->own_offset == 0 && A->R == 1,
-            EIG_ERR_SHAPE, std::string(who) + ": square single-rank matrix required");
+  check_square_single_rank(A, who, ": 1x1 blocks or square blocks FieldMatrix<double,b,b> with b = 2..4", true);
 }
 
 // Y = p(A) X: step k (k = d - 1 .. 0) writes panel (d - 1 - k) % 2 of {P0, P1}, chosen so that the last
@@ -80,22 +74,9 @@ long long apply_filter(const eig_mat_s &A, i64 m, const std::vector<double> &gam
   return (long long)d * filt_step_launches(A, m);
 }
 
-void upload(const std::vector<double> &h, double *d, hipStream_t s)
-{
-  EIG_HIP(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  EIG_HIP(hipStreamSynchronize(s));  // h is pageable and may go out of scope
-}
-
 bool cholqr(eig_slice_s &w, double *Z)
 {
-  CholQr2 q;
-  q.M = nullptr;
-  q.ctx = w.A->ctx;
-  q.b = w.m;
-  q.n = q.ld = w.n;
-  q.own = 0;
-  q.small = w.Qd();
-  q.chol = w.chol->d();
+  const CholQr2 q = cholqr_args(w.A->ctx, nullptr, w.m, w.n, w.n, 0, nullptr, w.Qd(), w.chol->d(), false);
   std::vector<double> R;
   return mcholqr2_mv(q, Z, Z, R, w.cholqr_recomputed);
 }
@@ -103,15 +84,13 @@ bool cholqr(eig_slice_s &w, double *Z)
 // R = AXp - X diag(theta) into `dst`, the column sums to the host
 void residual(eig_slice_s &w, const double *AXp, double *dst, hipStream_t s)
 {
-  launch_lobpcg_resid(w.A->ctx, w.n, w.n, w.m, AXp, w.X->d(), w.theta_d(), dst, w.sums_d(), s);
-  std::vector<double> sums((size_t)2 * w.m);
-  EIG_HIP(hipMemcpyAsync(sums.data(), w.sums_d(), sums.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  EIG_HIP(hipStreamSynchronize(s));
+  std::vector<double> sums;
+  residual_sums(w.A->ctx, w.n, w.n, w.m, AXp, w.X->d(), w.theta_d(), dst, w.sums_d(), sums, s);
   w.rr.assign(sums.begin(), sums.begin() + w.m);
   w.xx.assign(sums.begin() + w.m, sums.end());
 }
 
-bool accepted(const eig_slice_s &w, int j) { return w.theta[j] >= w.a && w.theta[j] <= w.b; }
+bool accepted(const eig_slice_s &w, int j) { return window_accept(w.theta[j], w.a, w.b); }
 
 int in_window(const eig_slice_s &w)
 {
@@ -120,19 +99,7 @@ int in_window(const eig_slice_s &w)
   return c;
 }
 
-bool all_converged(const eig_slice_s &w, double tol)
-{
-  if (w.rr.empty()) return false;
-  const double scale = std::max(std::fabs(w.a), std::fabs(w.b));
-  int cnt = 0;
-  for (int j = 0; j < w.m; ++j)
-  {
-    if (!accepted(w, j)) continue;
-    ++cnt;
-    if (!(std::sqrt(w.rr[j]) <= tol * std::max(std::fabs(w.theta[j]), scale) * std::sqrt(w.xx[j]))) return false;
-  }
-  return cnt > 0;
-}
+bool all_converged(const eig_slice_s &w, double tol) { return window_converged(w.theta, w.rr, w.xx, w.a, w.b, tol); }
 
 long long iterate(eig_slice_s &w, hipEvent_t *e)
 {
@@ -149,13 +116,8 @@ long long iterate(eig_slice_s &w, hipEvent_t *e)
   EIG_HIP(hipEventRecord(e[2], s));
   launch_spmm_mv8(*w.A, m, Y, W, s);
   launch_panel_gram(ctx, n, n, m, m, Y, W, w.Hd(), s);
-  std::vector<double> H((size_t)m * m), S;
-  EIG_HIP(hipMemcpyAsync(H.data(), w.Hd(), H.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  EIG_HIP(hipStreamSynchronize(s));
-  for (int r = 0; r < m; ++r)
-    for (int c = r + 1; c < m; ++c)
-      H[(size_t)r * m + c] = H[(size_t)c * m + r] = 0.5 * (H[(size_t)r * m + c] + H[(size_t)c * m + r]);
-  sym_eig(m, H, w.theta, S);  // theta ascending, column j of the row-major S = eigenvector j
+  std::vector<double> S;
+  small_ritz(m, w.Hd(), m, EIG_WHICH_SA, w.theta, S, s);  // theta ascending, column j of S = eigenvector j
   upload(S, w.Sd(), s);
   launch_panel_update(n, n, n, m, m, Y, w.Sd(), 1.0, 0.0, X, s);
   launch_panel_update(n, n, n, m, m, W, w.Sd(), 1.0, 0.0, AX, s);
@@ -253,8 +215,7 @@ extern "C" int eig_filter_count(eig_mat_t A, double a, double b, double lmin, do
     if (rc == EIG_OK) rc = eig_dot_diag_mv8(ctx, n, nvec, Z.d(), Y.d(), dp.d());
     if (rc != EIG_OK) throw Error(rc, ctx->last_error);
     std::vector<double> h((size_t)nvec);
-    EIG_HIP(hipMemcpyAsync(h.data(), dp.d(), h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    EIG_HIP(hipStreamSynchronize(ctx->stream));
+    download(h, dp.d(), ctx->stream);
     double sum = 0.0;
     for (double v : h) sum += v;
     *estimate = sum / nvec;
@@ -298,12 +259,7 @@ extern "C" int eig_slice_create(eig_mat_t A, double a, double b, double lmin, do
       if (X0)
         EIG_HIP(hipMemcpyAsync(w->X->d(), X0, bytes, hipMemcpyDeviceToDevice, s));
       else
-      {
-        // mt19937(seed) normals in MultiVector fill order (block, row, col) = the flat order (eig_random_mv8)
-        std::vector<double> h(w->panel());
-        host_random_normal((i64)h.size(), seed, h.data());
-        upload(h, w->X->d(), s);
-      }
+        random_block(ctx, n, m, seed, w->X->d());
       EIG_CHECK(cholqr(*w, w->X->d()), EIG_ERR_BREAKDOWN, "eig_slice_create: the start block is not of full rank");
     }
     catch (...)
@@ -323,20 +279,7 @@ extern "C" int eig_slice_step(eig_slice_t w, int max_iters, double tol, int *ite
     eig_ctx_t ctx = w->A->ctx;
     DeviceGuard dg(ctx->device);
     hipStream_t s = ctx->stream;
-    hipEvent_t ev[5];
-    std::vector<hipEvent_t> made;
-    struct EvGuard {
-      std::vector<hipEvent_t> &v;
-      ~EvGuard()
-      {
-        for (auto &e : v) (void)hipEventDestroy(e);
-      }
-    } evg{made};
-    for (auto &e : ev)
-    {
-      EIG_HIP(hipEventCreate(&e));
-      made.push_back(e);
-    }
+    TimingEvents ev(5);
     if (iters_done) *iters_done = 0;
     if (converged) *converged = 0;
     if (timing) std::memset(timing, 0, sizeof(*timing));
@@ -346,7 +289,7 @@ extern "C" int eig_slice_step(eig_slice_t w, int max_iters, double tol, int *ite
     bool conv = tol > 0.0 && all_converged(*w, tol);
     while (!conv && it < max_iters)
     {
-      launches += iterate(*w, ev);
+      launches += iterate(*w, ev.data());
       ++w->iters;
       ++it;
       if (iters_done) *iters_done = it;
@@ -401,25 +344,11 @@ extern "C" int eig_slice_ritz(eig_slice_t w, int *count, double *eval_host, doub
       residual(*w, w->W->d(), w->Y->d(), s);
       for (size_t q = 0; q < idx.size(); ++q) resid_host[q] = std::sqrt(w->rr[idx[q]]);
     }
-    if (evec_host)
-    {
-      std::vector<double> h(w->panel());
-      EIG_HIP(hipMemcpyAsync(h.data(), w->X->d(), h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-      EIG_HIP(hipStreamSynchronize(s));
-      for (size_t q = 0; q < idx.size(); ++q)
-      {
-        const int j = idx[q];
-        for (i64 r = 0; r < n; ++r) evec_host[q * (size_t)n + r] = h[((size_t)(j / 8) * n + r) * 8 + j % 8];
-      }
-    }
+    copy_evecs(ctx, w->X->d(), n, 0, n, (int)idx.size(), idx.data(), nullptr, evec_host);
   });
 }
 
 extern "C" int eig_slice_destroy(eig_slice_t w)
 {
-  if (!w) return EIG_OK;
-  (void)hipSetDevice(w->A->ctx->device);
-  (void)hipStreamSynchronize(w->A->ctx->stream);
-  delete w;
-  return EIG_OK;
+  return w ? destroy_workspace(w, w->A->ctx) : EIG_OK;
 }

@@ -15,7 +15,7 @@ import numpy as np
 import mg_ref
 import oracle
 
-REUSE_COND = 1e4  # blanczos.cpp kCholQrReuseCond
+REUSE_COND = 1e4  # subspace_host.h kCholQrReuseCond
 ORTH_TOL = 1e-10  # lobpcg.cpp kOrthTol: max |S^T M S - I| an iteration may enter its Rayleigh-Ritz with
 
 

@@ -1,6 +1,6 @@
 """numpy restatement of the multigrid inner solve (dune-eigensolver_amd/csrc/mg.cpp, k_mg.hip) --
 test infrastructure only: the same hierarchy (odd-index coarse nodes, trilinear P, Galerkin P^T A P
-mirrored from its upper triangle), the same Chebyshev-Jacobi recurrence (blanczos.cpp cheb_solve),
+mirrored from its upper triangle), the same Chebyshev-Jacobi recurrence (subspace.cpp cheb_solve),
 the same symmetric V-cycle and stationary iteration, in double precision with another rounding
 order (the device sums in another order / with FMA), so results agree to ~1e-13, not bitwise."""
 import numpy as np

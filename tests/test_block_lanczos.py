@@ -143,7 +143,7 @@ def test_block_lanczos_vs_recurrence_and_eigh(ctx):
 
 @pytest.mark.gpu
 def test_cholqr2_ill_conditioned_block(ctx):
-    """ADVICE r3 (blanczos.cpp mcholqr2): when the first CholQR pass's R is ill-conditioned (a block
+    """ADVICE r3 (subspace.cpp mcholqr2_mv): when the first CholQR pass's R is ill-conditioned (a block
     whose directions run out) the second pass recomputes M (Z R0^-1) instead of reusing (M Z) R0^-1,
     so the basis stays M-orthonormal to ~eps (reuse would leave ~eps cond(R0) = 1e-10).  The
     spectrum: two eigenvalue clusters of 300 (width 1e-6) and four single eigenvalues, so the
